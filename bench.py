@@ -3,7 +3,13 @@
 at 1/2/4/8 GPUs, with the HBM / xGMI roofline fraction).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--keys N_TOTAL] [--dtype i32|i64]
-                    [--dist uniform|zipf] [--path single|samplesort] [--no-cpu-baseline]
+                    [--dist uniform|zipf] [--path single|samplesort] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--legs ...]]
+
+A plain run sets up, warms up, times --steps sorts, writes the last one's keys if --dump-outputs is
+given, and prints the metric's line (metric, value, unit, ms_per_step, config).  --full adds, all
+outside the timed region: the verification, the roofline, the torch.sort comparison, the CPU
+baseline and the sample sort's extra legs, as described below.
 
 One step = one full sort of the synthetic batch, input already resident in HBM:
   single      (default at N = 1) dsort_sort_dev_copy: partition, tile sort and merge-path passes
@@ -16,10 +22,14 @@ One step = one full sort of the synthetic batch, input already resident in HBM:
 Ranks: `python bench.py --gpus N` spawns the N rank processes itself (subprocess, before any GPU
 call, rendezvous on 127.0.0.1); under torch.distributed.run it is one of them.  --gpus must equal
 the number of rank processes, and N GPUs must be visible.
-The sorted output is verified outside the timed region (ascending + multiset fingerprint + rank
-boundaries).
+The input depends on the arguments alone (splitmix64 of a fixed seed + the key's index), so two
+builds sort the same keys and --dump-outputs writes comparable files: DIR/sorted_keys.npy (float64;
+int64 keys as sorted_keys_hi.npy / sorted_keys_lo.npy) holds the sorted output of the last timed
+step, or above 2^22 values seeded blocks of it whose positions DIR/sample_blocks.npy lists.
+With --full the sorted output is verified outside the timed region (ascending + multiset
+fingerprint + rank boundaries).
 
-Rank 0 prints ONE JSON line with two extra objects:
+Rank 0 prints ONE JSON line, with --full with two extra objects:
   roofline      live HIP-event timing of every kernel of the sort (first-level histogram and
                 scatter, second-level partition, tile sort: algorithmic bytes = 1 or 2 x key
                 bytes per key) against 8 TB/s; `kernel` is the slowest of them (at N > 1 the
@@ -83,6 +93,14 @@ def parse(argv=None):
     ap.add_argument("--no-legs", dest="legs", action="store_const", const="none")
     ap.add_argument("--leg-timeout", type=float, default=180.0,
                     help="exchange deadline of a sort leg in seconds (the C5 leg gets 2x)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the metric's timed steps also run everything else this script measures or "
+                         "checks: the verification of the sorted output, the instrumented steps of the "
+                         "roofline, the torch.sort comparison, the CPU baseline and (sample sort) the extra legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the sorted keys of the last timed step to DIR/sorted_keys.npy (int64 keys: "
+                         "sorted_keys_hi.npy and sorted_keys_lo.npy) and their positions to "
+                         "DIR/sample_blocks.npy, as float64; a fixed, seeded sample of a larger output")
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args(argv)
 
@@ -492,6 +510,43 @@ def make_input(ctx, n, first, dtype, dist):
     return t
 
 
+# --dump-outputs: the sorted keys of the last timed step as float64 arrays, 32 MiB of them
+DUMP_BLOCK = 4096     # consecutive keys per sampled block
+DUMP_KEYS = 1 << 22   # float64 values written (int64 keys take two each)
+
+
+def sample_blocks(n, w):
+    """The [start, end) ranges of an n-key sorted output (w bytes per key) that --dump-outputs
+    writes: all of it when it fits, else equal strata of the output with one block of DUMP_BLOCK
+    consecutive keys at a seeded place in each; the first block is the output's head, the last
+    its tail.  Ascending, disjoint, and the same from run to run."""
+    cap = DUMP_KEYS // (w // 4)
+    if n <= cap:
+        return [(0, n)] if n else []
+    nb = cap // DUMP_BLOCK
+    stride = n // nb  # (> DUMP_BLOCK: n > cap)
+    offs = np.random.default_rng(SEED).integers(0, stride - DUMP_BLOCK + 1, nb)
+    starts = [i * stride + int(o) for i, o in enumerate(offs)]
+    starts[0], starts[-1] = 0, n - DUMP_BLOCK
+    return [(s, s + DUMP_BLOCK) for s in starts]
+
+
+def write_dump(path, blocks, pieces):
+    """DIR/sorted_keys.npy: the keys of `blocks` (pieces: one integer array per block) in ascending
+    position, as float64 -- exact for int32; int64 keys as sorted_keys_hi.npy (key >> 32) and
+    sorted_keys_lo.npy (key & 0xffffffff), both exact.  DIR/sample_blocks.npy: the blocks' start and
+    end positions in the whole sorted output, one row each."""
+    os.makedirs(path, exist_ok=True)
+    keys = np.concatenate(pieces) if pieces else np.zeros(0, np.int32)
+    assert keys.size == sum(e - s for s, e in blocks)
+    if keys.dtype.itemsize == 8:
+        np.save(os.path.join(path, "sorted_keys_hi.npy"), (keys >> 32).astype(np.float64))
+        np.save(os.path.join(path, "sorted_keys_lo.npy"), (keys & 0xFFFFFFFF).astype(np.float64))
+    else:
+        np.save(os.path.join(path, "sorted_keys.npy"), keys.astype(np.float64))
+    np.save(os.path.join(path, "sample_blocks.npy"), np.array(blocks, np.float64).reshape(-1, 2))
+
+
 def run_single(args):
     import torch
 
@@ -502,21 +557,22 @@ def run_single(args):
     w = 4 if args.dtype == "i32" else 8
     t_in = make_input(ctx, n, 0, args.dtype, args.dist)
     out = torch.empty_like(t_in)
-    fp_in = ctx.fingerprint(t_in)
+    if args.full:
+        fp_in = ctx.fingerprint(t_in)
     for _ in range(args.warmup):
         ctx.sort_dev(t_in, out)
     torch.cuda.synchronize()
-    if args.warmup == 0:  # still verify once, outside the timed region
-        ctx.sort_dev(t_in, out)
+    if args.full:  # the sorted output verified once, outside the timed region
+        if args.warmup == 0:
+            ctx.sort_dev(t_in, out)
+            torch.cuda.synchronize()
+        ok = ctx.descents(out) == 0 and ctx.fingerprint(out) == fp_in
+        if not ok:
+            raise SystemExit("bench: sorted output failed verification")
         torch.cuda.synchronize()
-    ok = ctx.descents(out) == 0 and ctx.fingerprint(out) == fp_in
-    if not ok:
-        raise SystemExit("bench: sorted output failed verification")
-    torch.cuda.synchronize()
     # the timed steps run back to back (a sort returns while its last kernels run; nothing is read
     # back in between) with no stage events (DSORT_OPT_STAGE_TIMING = 0: each event costs the GPU a
-    # few us between two kernels), then as many steps again, each with its HIP events and followed
-    # by a read of them, give the per-stage device times of the roofline (outside the timed region)
+    # few us between two kernels)
     ctx.set_option("stage_timing", 0)
     ctx.sort_dev(t_in, out)  # (untimed: the first sort of this mode)
     torch.cuda.synchronize()
@@ -525,6 +581,25 @@ def run_single(args):
         ctx.sort_dev(t_in, out)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
+    stats = ctx.stats()
+    k = {"passes": stats["merge_passes"], "tile": stats["tile_keys"], "w": w, "n": n}
+    if args.dump_outputs:  # (before anything else writes `out`: the last timed step's keys)
+        blocks = sample_blocks(n, w)
+        write_dump(args.dump_outputs, blocks, [torch.cat([out[s:e] for s, e in blocks]).cpu().numpy()] if blocks else [])
+    if args.full:
+        k.update(single_stage_times(args, ctx, t_in, out))
+    ctx.close()
+    if args.full:
+        del out
+        k["torch_sort_ms"] = torch_sort_ms(t_in)
+    return t1 - t0, k
+
+
+def single_stage_times(args, ctx, t_in, out):
+    """--full, after the timed steps of the one-GPU sort: as many steps again, each with its HIP
+    events and followed by a read of them, give the per-stage device times of the roofline."""
+    import torch
+
     ctx.set_option("stage_timing", 1)
     acc = {k: 0.0 for k in ("merge_kernel_ms", "block_sort_ms", "total_ms", "tile_sort_kernel_ms", "partition_ms",
                             "bucket_hist_ms", "bucket_scatter_ms", "sub_partition_ms")}
@@ -537,13 +612,18 @@ def run_single(args):
         npass += st["merge_passes"]
         tkeys += st["tile_sort_keys"]
     torch.cuda.synchronize()
-    stats = ctx.stats()
-    ctx.close()
-    # for context, not a baseline of the metric: the same keys through torch.sort (rocPRIM's radix
-    # sort of this image's PyTorch), outside the timed region
+    k = {key: v / max(args.steps, 1) for key, v in acc.items()}  # per step
+    k.update({"npass": npass, "tile_sort_keys": tkeys // max(args.steps, 1)})
+    return k
+
+
+def torch_sort_ms(t_in):
+    """--full: for context, not a baseline of the metric: the same keys through torch.sort
+    (PyTorch's rocPRIM radix sort), outside the timed region; None when it does not fit."""
+    import torch
+
     lib_ms = None
     try:
-        del out
         torch.cuda.empty_cache()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.sort(t_in)
@@ -556,11 +636,7 @@ def run_single(args):
         lib_ms = e0.elapsed_time(e1) / 3
     except RuntimeError:  # (out of memory on a smaller device: no comparison)
         lib_ms = None
-    k = {key: v / max(args.steps, 1) for key, v in acc.items()}  # per step
-    k["torch_sort_ms"] = lib_ms
-    k.update({"passes": stats["merge_passes"], "npass": npass, "tile": stats["tile_keys"], "w": w,
-              "tile_sort_keys": tkeys // max(args.steps, 1), "n": n})
-    return t1 - t0, k
+    return lib_ms
 
 
 def _sync_ok(dist, flag):
@@ -573,13 +649,38 @@ def _sync_ok(dist, flag):
     return bool(t.item())
 
 
-def measure_samplesort(ctx, dist, rank, world, n, dtype, distname, steps, warmup, strict=True):
+def dump_samplesort(ctx, dist, rank, world, n, w, ptr, nout, path):
+    """--dump-outputs of a sample sort: the ranks' slices in rank order are the sorted output; every
+    rank copies the part of each sampled block that lies in its slice, rank 0 writes them."""
+    counts = [None] * world
+    dist.all_gather_object(counts, int(nout))
+    off = sum(counts[:rank])
+    blocks = sample_blocks(n, w)
+    mine = []
+    for s, e in blocks:
+        a, b = max(s, off), min(e, off + nout)
+        if a < b:
+            h = np.empty(b - a, np.int32 if w == 4 else np.int64)
+            ctx.copy_d2h(h, ptr + (a - off) * w, (b - a) * w)
+            mine.append((a, h))
+    parts = [None] * world if rank == 0 else None
+    dist.gather_object(mine, parts, dst=0)
+    if rank == 0:
+        if sum(counts) != n:
+            raise SystemExit(f"bench: the ranks hold {sum(counts)} keys after the sort, not {n}")
+        write_dump(path, blocks, [h for _, h in sorted((p for ps in parts for p in ps), key=lambda p: p[0])])
+
+
+def measure_samplesort(ctx, dist, rank, world, n, dtype, distname, steps, warmup, strict=True, full=True,
+                       dump=None):
     """One sample-sort workload on the ranks' communicator: n keys in all, split into equal
     contiguous chunks (server.c:185-216), `warmup` untimed sorts, verification (local order, global
     multiset fingerprint, rank boundaries), `steps` timed sorts back to back between two barriers
     (no stage events), then `steps` instrumented sorts for the per-stage device times.  Returns
     (elapsed_max_over_ranks, verified, per_rank table (PR_* columns), key bytes, error).  strict:
-    a library error raises (the metric line); else every rank returns it (an extra leg)."""
+    a library error raises (the metric line); else every rank returns it (an extra leg).  full
+    False (a plain run): no verification (verified is None) and no instrumented sorts (the table's
+    times are 0).  dump: the directory rank 0 writes the last timed sort's keys to (write_dump)."""
     import torch
 
     import dsort
@@ -604,7 +705,7 @@ def measure_samplesort(ctx, dist, rank, world, n, dtype, distname, steps, warmup
 
     def prepare():
         st_in["t"] = make_input(ctx, sz, first, dtype, distname)
-        st_in["fp"] = ctx.fingerprint(st_in["t"])
+        st_in["fp"] = ctx.fingerprint(st_in["t"]) if full else None
         for _ in range(max(warmup, 1)):
             st_in["res"] = ctx.sample_sort_dev(st_in["t"])
         ctx.synchronize()
@@ -612,24 +713,26 @@ def measure_samplesort(ctx, dist, rank, world, n, dtype, distname, steps, warmup
     if not _sync_ok(dist, guarded(prepare)):
         return None, False, None, w, err or "a peer failed"
     t_in, in_fp = st_in["t"], st_in["fp"]
-    ptr, nout = st_in["res"]
-    # verification outside the timed region: local order, global multiset, rank boundaries
-    c, fs, fx = dsort.U64(), dsort.U64(), dsort.U64()
-    ctx.check(getattr(ctx.lib, f"dsort_count_descents_{dtype}")(ctx.h, ptr, nout, ctypes.byref(c)))
-    ctx.check(getattr(ctx.lib, f"dsort_fingerprint_{dtype}")(ctx.h, ptr, nout, ctypes.byref(fs), ctypes.byref(fx)))
-    ends = np.zeros(2, np.int64)
-    if nout:
-        hb = np.zeros(1, np.int64 if dtype == "i64" else np.int32)
-        ctx.copy_d2h(hb, ptr, hb.itemsize)
-        ends[0] = hb[0]
-        ctx.copy_d2h(hb, ptr + (nout - 1) * hb.itemsize, hb.itemsize)
-        ends[1] = hb[0]
-    M = 0xFFFFFFFFFFFFFFFF
-    info = torch.tensor([c.value, nout, ends[0], ends[1]], dtype=torch.int64)
-    allinfo = [torch.zeros_like(info) for _ in range(world)]
-    dist.all_gather(allinfo, info)
-    fps = [None] * world
-    dist.all_gather_object(fps, (in_fp[0], in_fp[1], fs.value, fx.value))
+    allinfo, fps = None, None
+    if full:
+        ptr, nout = st_in["res"]
+        # verification outside the timed region: local order, global multiset, rank boundaries
+        c, fs, fx = dsort.U64(), dsort.U64(), dsort.U64()
+        ctx.check(getattr(ctx.lib, f"dsort_count_descents_{dtype}")(ctx.h, ptr, nout, ctypes.byref(c)))
+        ctx.check(getattr(ctx.lib, f"dsort_fingerprint_{dtype}")(ctx.h, ptr, nout, ctypes.byref(fs), ctypes.byref(fx)))
+        ends = np.zeros(2, np.int64)
+        if nout:
+            hb = np.zeros(1, np.int64 if dtype == "i64" else np.int32)
+            ctx.copy_d2h(hb, ptr, hb.itemsize)
+            ends[0] = hb[0]
+            ctx.copy_d2h(hb, ptr + (nout - 1) * hb.itemsize, hb.itemsize)
+            ends[1] = hb[0]
+        M = 0xFFFFFFFFFFFFFFFF
+        info = torch.tensor([c.value, nout, ends[0], ends[1]], dtype=torch.int64)
+        allinfo = [torch.zeros_like(info) for _ in range(world)]
+        dist.all_gather(allinfo, info)
+        fps = [None] * world
+        dist.all_gather_object(fps, (in_fp[0], in_fp[1], fs.value, fx.value))
     ctx.set_option("stage_timing", 0)  # (no stage events in the timed steps, as at N = 1)
     torch.cuda.synchronize()
     dist.barrier()
@@ -637,7 +740,7 @@ def measure_samplesort(ctx, dist, rank, world, n, dtype, distname, steps, warmup
 
     def timed_steps():
         for _ in range(steps):
-            ctx.sample_sort_dev(t_in)
+            st_in["res"] = ctx.sample_sort_dev(t_in)
         torch.cuda.synchronize()
 
     ok_t = guarded(timed_steps)
@@ -648,6 +751,8 @@ def measure_samplesort(ctx, dist, rank, world, n, dtype, distname, steps, warmup
         return None, False, None, w, err or "a peer failed"
     el = torch.tensor([t1 - t0], dtype=torch.float64)
     dist.all_reduce(el, op=dist.ReduceOp.MAX)
+    if dump:
+        dump_samplesort(ctx, dist, rank, world, n, w, *st_in["res"], dump)
     # per-stage device times from as many instrumented steps again (outside the timed region)
     timed = ("exchange_ms", "alltoall_ms", "final_merge_ms", "merge_kernel_ms", "tile_sort_kernel_ms",
              "bucket_hist_ms", "bucket_scatter_ms", "sub_partition_ms", "total_ms")
@@ -667,7 +772,11 @@ def measure_samplesort(ctx, dist, rank, world, n, dtype, distname, steps, warmup
             acc["exchange_path"] = st["exchange_path"]
         torch.cuda.synchronize()
 
-    if not _sync_ok(dist, guarded(instrumented)):
+    def counters_only():  # (a plain run: what the result line's config names, no stage times)
+        st = ctx.stats()
+        acc["sent"], acc["exchange_path"] = st["keys_sent"] * steps, st["exchange_path"]
+
+    if not _sync_ok(dist, guarded(instrumented if full else counters_only)):
         return None, False, None, w, err or "a peer failed"
     # per-rank figures of the roofline, gathered (rank 0 reports the slowest rank)
     st_n = max(steps, 1)
@@ -679,6 +788,10 @@ def measure_samplesort(ctx, dist, rank, world, n, dtype, distname, steps, warmup
                         dtype=torch.float64)
     everyone = [torch.zeros_like(mine) for _ in range(world)]
     dist.all_gather(everyone, mine)
+    if not full:
+        del t_in, st_in
+        torch.cuda.empty_cache()
+        return float(el.item()), None, torch.stack(everyone).numpy(), w, None
     A = torch.stack(allinfo)
     ok = bool((A[:, 0] == 0).all()) and int(A[:, 1].sum()) == n
     ok &= sum(f[0] for f in fps) & M == sum(f[2] for f in fps) & M
@@ -715,7 +828,8 @@ def leg_plan(world):
 
 
 def legs_wanted(args):
-    if args.legs in ("", "none"):
+    """The extra legs of this run: none without --full (a plain run measures the metric alone)."""
+    if not args.full or args.legs in ("", "none"):
         return []
     want = LEG_NAMES if args.legs == "all" else tuple(x for x in args.legs.split(",") if x)
     bad = [x for x in want if x not in LEG_NAMES]
@@ -733,7 +847,7 @@ def leg_summary(name, spec, world, steps, res):
         out.update({"verified": False, "error": err or "failed"})
         return out
     ns = argparse.Namespace(keys=spec["keys"], steps=steps, warmup=1, dtype=spec["dtype"], dist=spec["dist"],
-                            no_cpu_baseline=True)
+                            no_cpu_baseline=True, full=True)
     full = summarize_multi(ns, world, elapsed, per_rank, w)
     out.update({"verified": bool(ok), "value": full["value"], "unit": "keys/s", "ms_per_step": full["ms_per_step"],
                 "workload": full["config"]["workload"], "roofline": full["roofline"]})
@@ -790,7 +904,8 @@ def run_multi(args, rank, world):
     dist.broadcast_object_list(uid, src=0)
     ctx.comm_init(world, rank, uid[0])
     elapsed, ok, per_rank, w, _ = measure_samplesort(ctx, dist, rank, world, args.keys, args.dtype, args.dist,
-                                                     args.steps, args.warmup)
+                                                     args.steps, args.warmup, full=args.full,
+                                                     dump=args.dump_outputs)
     legs = {}
     plan = leg_plan(world)
     for name in legs_wanted(args):
@@ -864,6 +979,9 @@ def report_single(args, elapsed, k):
     result["config"] = {"workload": f"{cfg} single-GPU sort of {n} {args.dist} {result['dtype']} keys "
                                     f"(BASELINE metric size); tile {k['tile']} keys, {k['passes']} merge passes",
                         "keys": n, "parallelism": "1 GPU"}
+    if not args.full:  # a plain run: the metric alone
+        print(json.dumps(result), flush=True)
+        return
     w = k["w"]
     stages = stage_roofline(k, w, n, args.dist, drop_pure=True)
     if stages:  # the bucketed path: the dominant kernel is the slowest stage
@@ -943,7 +1061,7 @@ def report_multi(args, world, elapsed, per_rank, w, legs=None):
     result = summarize_multi(args, world, elapsed, per_rank, w)
     if legs:
         result["legs"] = legs
-    if not args.no_cpu_baseline and args.dtype == "i32":
+    if args.full and not args.no_cpu_baseline and args.dtype == "i32":
         # the reference's CPU path beside the N-GPU number (rank 0, after the timed region and the
         # other ranks' exit): the same leg as N = 1
         result["cpu_baseline"] = cpu_baseline(args.cpu_sample_keys, args.keys)
@@ -963,6 +1081,8 @@ def summarize_multi(args, world, elapsed, per_rank, w):
                                     f"(equal contiguous chunks; {how})",
                         "keys": n, "keys_per_gpu": n // world, "parallelism": f"samplesort x{world}",
                         "exchange_path": "bucket exchange" if bx else "sort + merge"}
+    if not args.full:  # a plain run: the metric alone (its per-rank table holds no stage times)
+        return result
     # the local sort's stages on every rank (HIP events); the dominant kernel is the slowest stage
     # of the slowest rank
     best = None
@@ -1129,6 +1249,8 @@ def run_codec(args):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
+    if args.dump_outputs and (args.kill_rank is not None or args.codec):
+        raise SystemExit("bench: --dump-outputs writes the sorted keys of the sort paths (not --kill-rank / --codec)")
     if args.kill_rank is not None:
         if "WORLD_SIZE" in os.environ:
             raise SystemExit("--kill-rank runs its own master and workers: launch it without torchrun")
@@ -1156,7 +1278,7 @@ def main(argv=None):
         return 0
     elapsed, ok, per_rank, w, legs = run_multi(args, rank, world)
     if rank == 0:
-        if not ok:
+        if args.full and not ok:
             raise SystemExit("bench: distributed output failed verification")
         report_multi(args, world, elapsed, per_rank, w, legs)
     return 0

@@ -39,7 +39,7 @@ def test_report_multi_carries_roofline_all_kernels_and_cpu_baseline(capsys):
     import bench
 
     world, n = 4, 1 << 30
-    args = bench.parse(["--gpus", str(world), "--steps", "5", "--cpu-sample-keys", str(1 << 16)])
+    args = bench.parse(["--gpus", str(world), "--steps", "5", "--cpu-sample-keys", str(1 << 16), "--full"])
     bench.report_multi(args, world, 5 * 2.1e-3, _per_rank(world, n, 4), 4)
     line = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
@@ -114,10 +114,11 @@ def test_multi_line_carries_c3_c4_c5_legs(capsys):
     assert plan["c5"]["kill_rank"] == 3 and plan["c5"]["workers"] == 8 and plan["c5"]["transport"] == "rccl"
     assert bench.leg_plan(2)["c3"]["keys"] == 1 << 30 and bench.leg_plan(2)["c5"]["kill_rank"] == 1
     assert bench.leg_plan(1)["c5"]["transport"] == "relay"  # (one GPU: two workers share it)
-    args = bench.parse(["--gpus", str(world), "--steps", "5", "--no-cpu-baseline"])
+    args = bench.parse(["--gpus", str(world), "--steps", "5", "--no-cpu-baseline", "--full"])
     assert bench.legs_wanted(args) == ["c3", "c4", "c5"]
-    assert bench.legs_wanted(bench.parse(["--no-legs"])) == []
-    assert bench.legs_wanted(bench.parse(["--legs", "c4"])) == ["c4"]
+    assert bench.legs_wanted(bench.parse(["--full", "--no-legs"])) == []
+    assert bench.legs_wanted(bench.parse(["--full", "--legs", "c4"])) == ["c4"]
+    assert bench.legs_wanted(bench.parse(["--legs", "c4"])) == []  # (a plain run measures the metric alone)
     c3 = bench.leg_summary("c3", plan["c3"], world, 3, (3 * 6.0e-3, True, _per_rank(world, 1 << 32, 4), 4, None))
     c4 = bench.leg_summary("c4", plan["c4"], world, 3, (3 * 2.0e-3, True, _per_rank(world, 1 << 30, 8), 8, None))
     bad = bench.leg_summary("c4", plan["c4"], world, 3, (None, False, None, 8, "rank 2: ETIMEOUT"))
@@ -136,3 +137,53 @@ def test_multi_line_carries_c3_c4_c5_legs(capsys):
     assert "all_kernels_frac" not in legs["c4"]["roofline"] and "all_kernels_frac_estimate" not in legs["c4"]["roofline"]
     assert legs["c5"]["verified"] and legs["c5"]["unit"] == "ms"
     assert bad["verified"] is False and "ETIMEOUT" in bad["error"]
+
+
+def test_plain_multi_line_is_the_metric_alone(capsys):
+    """Without --full the N > 1 line carries the metric (value, ms_per_step, config) and none of
+    what takes runs of its own: no roofline, no CPU baseline, no legs."""
+    sys.path.insert(0, REPO)
+    import bench
+
+    args = bench.parse(["--gpus", "2", "--steps", "4"])
+    assert not args.full and bench.legs_wanted(args) == []
+    bench.report_multi(args, 2, 4 * 4e-3, _per_rank(2, 1 << 30, 4), 4, {})
+    d = json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][-1])
+    assert d["metric"] == "sorted keys/sec (int32, 2^30 keys)" and d["unit"] == "keys/s" and d["dtype"] == "int32"
+    assert d["higher_is_better"] is True and d["steps"] == 4 and abs(d["ms_per_step"] - 4.0) < 1e-9
+    assert abs(d["value"] - (1 << 30) / 4e-3) < 1e3 and d["config"]["exchange_path"] == "bucket exchange"
+    assert not {"roofline", "cpu_baseline", "legs"} & set(d)
+
+
+def test_dump_sample_blocks_are_fixed_disjoint_and_bounded():
+    """--dump-outputs: the whole output when it fits, else seeded blocks that are the same on every
+    call, ascending, disjoint, inside the output, start at its head and end at its tail, and hold
+    at most 2^22 float64 values (int64 keys take two each)."""
+    sys.path.insert(0, REPO)
+    import bench
+
+    assert bench.sample_blocks(0, 4) == [] and bench.sample_blocks(5, 4) == [(0, 5)]
+    assert bench.sample_blocks(1 << 22, 4) == [(0, 1 << 22)] and bench.sample_blocks(1 << 21, 8) == [(0, 1 << 21)]
+    for n, w in (((1 << 22) + 1, 4), ((1 << 21) + 1, 8), ((1 << 22) + 12345, 4), (1 << 30, 4), (1 << 30, 8), (1 << 32, 4)):
+        b = bench.sample_blocks(n, w)
+        assert b == bench.sample_blocks(n, w)
+        assert b[0][0] == 0 and b[-1][1] == n
+        assert all(e - s == bench.DUMP_BLOCK for s, e in b)
+        assert all(b[i][1] <= b[i + 1][0] for i in range(len(b) - 1))
+        assert sum(e - s for s, e in b) * (w // 4) == 1 << 22
+
+
+def test_write_dump_files_are_exact_float64(tmp_path):
+    sys.path.insert(0, REPO)
+    import bench
+
+    k32 = np.array([-(2**31), -1, 0, 7, 2**31 - 1], np.int32)
+    bench.write_dump(str(tmp_path / "a"), [(0, 2), (7, 10)], [k32[:2], k32[2:]])
+    got = np.load(tmp_path / "a" / "sorted_keys.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.int64), k32.astype(np.int64))
+    assert np.array_equal(np.load(tmp_path / "a" / "sample_blocks.npy"), np.array([[0, 2], [7, 10]], np.float64))
+    k64 = np.array([-(2**63), -(2**53) - 1, -1, 0, 2**53 + 1, 2**63 - 1], np.int64)
+    bench.write_dump(str(tmp_path / "b"), [(0, 6)], [k64])
+    hi, lo = np.load(tmp_path / "b" / "sorted_keys_hi.npy"), np.load(tmp_path / "b" / "sorted_keys_lo.npy")
+    assert hi.dtype == lo.dtype == np.float64 and (lo >= 0).all() and (lo < 2**32).all()
+    assert np.array_equal((hi.astype(np.int64) << 32) | lo.astype(np.int64), k64)
