@@ -1173,7 +1173,7 @@ int dsort_finalize(dsort_ctx *ctx) {
     flush_later(ctx);
     void *bufs[] = {ctx->scratch, ctx->scratch2, ctx->splits, ctx->groups, ctx->io, ctx->io2, ctx->red,
                     ctx->local, ctx->recv, ctx->recv2, ctx->small, ctx->text_status,
-                    ctx->bucket, ctx->sub, ctx->sub_alt, ctx->stmp, ctx->bxs, ctx->tfb, ctx->fence};
+                    ctx->bucket, ctx->sub, ctx->sub_alt, ctx->stmp, ctx->bxs, ctx->tfb, ctx->fence, ctx->pairs};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->red_host) (void)hipHostFree(ctx->red_host);
@@ -1194,6 +1194,8 @@ int dsort_finalize(dsort_ctx *ctx) {
         if (e) (void)hipEventDestroy(e);
     if (ctx->xs) (void)hipStreamDestroy(ctx->xs);
     if (ctx->done_ev) (void)hipEventDestroy(ctx->done_ev);
+    for (auto &e : ctx->pairs_ev)
+        if (e) (void)hipEventDestroy(e);
     for (auto &e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : ctx->kev)

@@ -100,6 +100,10 @@ struct dsort_ctx {
     size_t io_bytes = 0;
     void *io2 = nullptr;
     size_t io2_bytes = 0;
+    void *pairs = nullptr;     // packed (key, value) words of the pair sort (dsort_pairs.hip): 8 B each
+    size_t pairs_bytes = 0;
+    hipEvent_t pairs_ev[4] = {};  // around its pack, sort and unpack legs (created on first use)
+    bool pairs_ev_ok = false;     // ... all four recorded by the last pair sort
     void *bucket = nullptr;       // partition pass of the bucketed int32 sort (dsort_bucket.h)
     size_t bucket_bytes = 0;
     void *bucket_host = nullptr;  // pinned: bucket starts
@@ -240,6 +244,12 @@ void fault_point(dsort_ctx *ctx, hipStream_t s, int stage);
 // Kill points of a top-level sort of n keys of key_bytes bytes under `opt` (the bucketed path
 // without the second level has data-dependent merge passes: the guaranteed minimum).
 int sort_stages(const dsort_opts &opt, uint64_t n, int key_bytes);
+// The cross-stream rule of the shared arenas (dsort_ctx::done_ev): a top-level call waits on its
+// stream for the context's previous call when that ran on another stream (order_begin), and marks
+// its own end (order_end).  sort_device and merge_device bracket themselves; a call that uses an
+// arena around them (the pair sort) brackets its whole sequence as well.
+int order_begin(dsort_ctx *ctx, hipStream_t s);
+int order_end(dsort_ctx *ctx, hipStream_t s);
 // Host waits of the sort: blocking, or (ctx->poll_waits) polling with the abort flag and deadline
 // (DSORT_ECOMM / DSORT_ETIMEOUT).
 int sync_event(dsort_ctx *ctx, hipEvent_t e, const char *what);

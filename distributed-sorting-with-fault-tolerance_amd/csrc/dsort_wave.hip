@@ -3196,12 +3196,12 @@ int sort_stages(const dsort_opts &opt, uint64_t n, int key_bytes) {
 // A top-level call first waits (on the device) for the context's previous call when that ran on
 // another stream, and marks its own end: the calls share the context's arenas and return while
 // their last kernels still run.
-static int order_begin(dsort_ctx *ctx, hipStream_t s) {
+int order_begin(dsort_ctx *ctx, hipStream_t s) {
     if (ctx->nested) return DSORT_OK;
     if (ctx->done_pending && ctx->done_stream != s) DSORT_HIP(ctx, hipStreamWaitEvent(s, ctx->done_ev, 0));
     return DSORT_OK;
 }
-static int order_end(dsort_ctx *ctx, hipStream_t s) {
+int order_end(dsort_ctx *ctx, hipStream_t s) {
     if (ctx->nested) return DSORT_OK;
     if (!ctx->done_ev && hipEventCreateWithFlags(&ctx->done_ev, hipEventDisableTiming) != hipSuccess)
         return set_err(ctx, DSORT_EHIP, "hipEventCreate");

@@ -43,6 +43,7 @@ EXPORTS = [
     "dsort_copy_h2d", "dsort_copy_d2h", "dsort_copy_d2d", "dsort_host_register",
     "dsort_host_unregister", "dsort_write_text_i32", "dsort_format_text_dev_i32",
     "dsort_parse_text_dev_i32", "dsort_parse_text_i32", "dsort_format_text_i32",
+    "dsort_argsort_dev_i32", "dsort_sort_pairs_dev_i32", "dsort_gather_dev", "dsort_argsort_i32",
 ]
 
 
@@ -255,6 +256,10 @@ def load():
         "dsort_parse_text_dev_i32": (ctypes.c_int, [P, P, SZ, P, SZ, ctypes.POINTER(SZ), P]),
         "dsort_parse_text_i32": (ctypes.c_int, [P, ctypes.c_char_p, SZ, P, SZ, ctypes.POINTER(SZ)]),
         "dsort_format_text_i32": (ctypes.c_int, [P, P, SZ, P, SZ, ctypes.POINTER(SZ)]),
+        "dsort_argsort_dev_i32": (ctypes.c_int, [P, P, P, P, SZ, P]),
+        "dsort_sort_pairs_dev_i32": (ctypes.c_int, [P, P, P, P, P, SZ, P]),
+        "dsort_gather_dev": (ctypes.c_int, [P, P, P, P, SZ, ctypes.c_int, P]),
+        "dsort_argsort_i32": (ctypes.c_int, [P, P, P, P, SZ]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -446,6 +451,69 @@ class Context:
         self.check(getattr(self.lib, f"dsort_merge_dev_{sfx}")(self.h, t.data_ptr(), ctypes.cast(la, P), k,
                                                                 out.data_ptr(), self._stream()))
         return out
+
+    # ---------------- argsort, key-value sort, gather (int32 keys; dsort.h, ABI 7) --------
+    @staticmethod
+    def _i32(t, what, n=None):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1:
+            raise DsortError(f"{what}: a contiguous 1-d int32 tensor is required")
+        if n is not None and t.numel() != n:
+            raise DsortError(f"{what}: {t.numel()} elements, expected {n}")
+        return t
+
+    def argsort_dev(self, keys, idx_out=None, keys_out=None):
+        """Stable argsort of an int32 CUDA tensor (dsort_argsort_dev_i32): returns
+        (keys_out, idx).  idx[j] is the position in `keys` of the j-th smallest key, equal keys
+        in input order.  idx is an int32 tensor holding the uint32 bit pattern (torch has no
+        uint32 arithmetic): non-negative, and usable as an index, for n < 2^31.  keys_out=None:
+        the sorted keys are not produced (None is returned for them); keys_out may be `keys`."""
+        n = self._i32(keys, "keys").numel()
+        if idx_out is None:
+            idx_out = torch.empty(n, dtype=torch.int32, device=keys.device)
+        self._i32(idx_out, "idx_out", n)
+        ko = None if keys_out is None else self._i32(keys_out, "keys_out", n).data_ptr()
+        self.check(self.lib.dsort_argsort_dev_i32(self.h, keys.data_ptr(), ko, idx_out.data_ptr(), n,
+                                                  self._stream()))
+        return keys_out, idx_out
+
+    def sort_pairs_dev(self, keys, vals, keys_out=None, vals_out=None):
+        """Key-value sort of int32 CUDA tensors (dsort_sort_pairs_dev_i32): ascending by key, equal
+        keys by value as UNSIGNED 32-bit.  In place when the outputs are None.  Returns
+        (keys_out, vals_out)."""
+        n = self._i32(keys, "keys").numel()
+        self._i32(vals, "vals", n)
+        keys_out = keys if keys_out is None else self._i32(keys_out, "keys_out", n)
+        vals_out = vals if vals_out is None else self._i32(vals_out, "vals_out", n)
+        self.check(self.lib.dsort_sort_pairs_dev_i32(self.h, keys.data_ptr(), vals.data_ptr(), keys_out.data_ptr(),
+                                                     vals_out.data_ptr(), n, self._stream()))
+        return keys_out, vals_out
+
+    def gather_dev(self, src, idx, out):
+        """out[i] = src[idx[i]] along dim 0 (dsort_gather_dev).  A record is one row of `src`:
+        element_size * the trailing dimensions, which must be 4, 8 or 16 bytes.  idx: int32 (the
+        argsort's uint32 bit pattern)."""
+        n = self._i32(idx, "idx").numel()
+        if not src.is_contiguous() or not out.is_contiguous() or src.dim() < 1:
+            raise DsortError("gather: contiguous tensors are required")
+        rec = src.element_size()
+        for d in src.shape[1:]:
+            rec *= int(d)
+        if rec not in (4, 8, 16):
+            raise DsortError(f"gather: records of {rec} bytes (4, 8 or 16)")
+        if out.dtype != src.dtype or tuple(out.shape) != (n,) + tuple(src.shape[1:]):
+            raise DsortError("gather: out must hold len(idx) records of src's type and row shape")
+        self.check(self.lib.dsort_gather_dev(self.h, src.data_ptr(), idx.data_ptr(), out.data_ptr(), n, rec,
+                                             self._stream()))
+        return out
+
+    def argsort(self, keys):
+        """Host form (dsort_argsort_i32): stable argsort of a numpy int32 array; returns
+        (sorted_keys, idx) as new arrays, idx of dtype uint32."""
+        keys = np.ascontiguousarray(keys, np.int32)
+        out = np.empty_like(keys)
+        idx = np.empty(keys.size, np.uint32)
+        self.check(self.lib.dsort_argsort_i32(self.h, _ptr(keys), _ptr(out), _ptr(idx), keys.size))
+        return out, idx
 
     def gen_uniform(self, t, seed, first=0):
         sfx = self._tsfx(t)

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DSORT_ABI_VERSION 6
+#define DSORT_ABI_VERSION 7
 
 #define DSORT_OK 0
 #define DSORT_EINVAL (-1)   /* bad argument */
@@ -203,6 +203,37 @@ int dsort_sort_dev_copy_i32(dsort_ctx *ctx, const int32_t *d_in, int32_t *d_out,
                             void *stream);
 int dsort_sort_dev_copy_i64(dsort_ctx *ctx, const int64_t *d_in, int64_t *d_out, size_t n,
                             void *stream);
+
+/* ---------------------------------------------------------------- argsort, pairs ----- */
+/* ABI 7: the permutation of a sort, and records of a key and a payload.  int32 keys only, with a
+ * 32-bit value; wider payloads follow their key by an argsort and dsort_gather_dev.  A key and
+ * its value are packed into one int64, (int64)key << 32 | (uint32)value, which the int64 sort
+ * orders by key, then by value as unsigned.  Memory: an arena of 8 * n bytes in the context
+ * (grow-only, like the others), on top of the int64 sort's own scratch for n keys.  int64 keys
+ * with a payload are not offered: they would need a 128-bit composite.  All device pointers need
+ * the alignment of their elements only (records of dsort_gather_dev: 4 bytes).
+ * DSORT_OPT_KILL_AFTER_STAGE acts as on an int64 sort of n keys: dsort_sort_stages(ctx, n, 8, ..)
+ * gives the stage count, and with DSORT_ESTAGE the outputs are valid as for a sort.
+ * dsort_get_stats afterwards shows that int64 sort's statistics (keys_in = keys_out = n). */
+
+/* Stable argsort: d_idx_out[j] = position in d_keys of the j-th smallest key, equal keys in
+ * input order; d_keys_out (NULL: not wanted; may equal d_keys) gets the sorted keys.  n <= 2^32
+ * (else DSORT_EINVAL, before any memory is touched).  Asynchronous on `stream`. */
+int dsort_argsort_dev_i32(dsort_ctx *ctx, const int32_t *d_keys, int32_t *d_keys_out,
+                          uint32_t *d_idx_out, size_t n, void *stream);
+/* Key-value sort: ascending by key, equal keys ascending by value as UNSIGNED 32-bit
+ * (deterministic, independent of input order).  Outputs may alias the inputs; d_keys_out may be
+ * NULL (not wanted).  No bound on n beyond memory.  Asynchronous on `stream`. */
+int dsort_sort_pairs_dev_i32(dsort_ctx *ctx, const int32_t *d_keys_in, const uint32_t *d_vals_in,
+                             int32_t *d_keys_out, uint32_t *d_vals_out, size_t n, void *stream);
+/* d_dst[i] = d_src[d_idx[i]], i < n, for records of elem_bytes in {4, 8, 16} (else DSORT_EINVAL);
+ * no overlap; an index >= the source length is the caller's error (not checked).  Applies an
+ * argsort's permutation to the caller's payload records.  Asynchronous on `stream`. */
+int dsort_gather_dev(dsort_ctx *ctx, const void *d_src, const uint32_t *d_idx, void *d_dst,
+                     size_t n, int elem_bytes, void *stream);
+/* Host form (synchronous, staged through the context's arenas like dsort_sort_i32): writes
+ * idx (n entries) and, if non-NULL, keys_out (may equal keys).  n <= 2^32. */
+int dsort_argsort_i32(dsort_ctx *ctx, const int32_t *keys, int32_t *keys_out, uint32_t *idx, size_t n);
 
 /* ---------------------------------------------------------------- master merge ------- */
 /* Drop-in for the merge half of merge_chunks (server.c:481-515): merges k sorted host runs

@@ -1,0 +1,136 @@
+#!/usr/bin/env python3
+"""Stable argsort of int32 keys (dsort_argsort_dev_i32) measured on one MI355X, keys resident in HBM.
+
+For uniform keys at every --log2 size (default 2^28 and 2^30):
+
+  argsort_ms        dsort_argsort_dev_i32 (sorted keys + indices) back to back, HIP events around
+                    --steps calls on one stream;
+  legs_ms           its pack, int64 sort and unpack legs, from the HIP events the library records
+                    between them (dsort_pairs_leg_ms), median over --steps separate calls;
+  torch_sort_ms     torch.sort(stable=True) of the same resident keys: the same (key, index) job;
+  memcpy            a device-to-device hipMemcpyAsync (torch's same-device copy_ of a contiguous
+                    tensor) that moves the byte total of each streaming leg -- pack reads 4n and
+                    writes 8n, unpack reads 8n and writes 8n, so copies of 6n and 8n bytes -- and each
+                    leg's rate as a fraction of that copy's rate in this same run.
+
+    python scripts/bench_pairs.py [--log2 28 30] [--steps 10] [--warmup 2] [--out profiles/pairs_bench.json]
+
+Writes the JSON file and prints one summary line.  No GPU: fails (there is nothing to measure).
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "distributed-sorting-with-fault-tolerance_amd"))
+
+
+def timed(torch, fn, steps, warmup):
+    """ms per call of fn, `steps` calls back to back between two events."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def bench_size(torch, ctx, n, steps, warmup):
+    keys = torch.empty(n, dtype=torch.int32, device="cuda")
+    ctx.gen_uniform(keys, 0x5EED2026, 0)
+    out = torch.empty_like(keys)
+    idx = torch.empty_like(keys)
+
+    argsort_ms = timed(torch, lambda: ctx.argsort_dev(keys, idx_out=idx, keys_out=out), steps, warmup)
+
+    leg_fn = ctx.lib.dsort_pairs_leg_ms  # not in dsort.h: the bench's view of the legs' events
+    leg_fn.restype = ctypes.c_int
+    leg_fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+    legs = []
+    for _ in range(steps):
+        ctx.argsort_dev(keys, idx_out=idx, keys_out=out)
+        ms = (ctypes.c_double * 3)()
+        ctx.check(leg_fn(ctx.h, ms))
+        legs.append(tuple(ms))
+    pack_ms, sort_ms, unpack_ms = (statistics.median(x[i] for x in legs) for i in range(3))
+    stats = ctx.stats()
+
+    tvals, tidx = torch.sort(keys, stable=True)  # also the check
+    exact = bool(torch.equal(out, tvals) and torch.equal(idx.to(torch.int64), tidx))
+    del tvals, tidx
+    torch_ms = timed(torch, lambda: torch.sort(keys, stable=True), max(3, steps // 2), 1)
+    del out, idx
+    torch.cuda.empty_cache()
+
+    copies = {}
+    for leg, total in (("pack", 12 * n), ("unpack", 16 * n)):
+        src = torch.empty(total // 2, dtype=torch.uint8, device="cuda")
+        dst = torch.empty_like(src)
+        src.zero_()
+        copies[leg] = timed(torch, lambda: dst.copy_(src), steps, warmup)
+        del src, dst
+        torch.cuda.empty_cache()
+    del keys
+    torch.cuda.empty_cache()
+
+    gbs = lambda b, ms: b / (ms * 1e-3) / 1e9  # noqa: E731
+    r4 = lambda x: round(x, 4)  # noqa: E731
+    return {
+        "n": n,
+        "argsort_ms": r4(argsort_ms),
+        "argsort_gkeys_per_s": r4(n / (argsort_ms * 1e-3) / 1e9),
+        "legs_ms": {"pack": r4(pack_ms), "sort_i64": r4(sort_ms), "unpack": r4(unpack_ms)},
+        "inner_sort_stats": {k: stats[k] for k in ("total_ms", "merge_passes", "tile_keys", "first_level_map")},
+        "torch_sort_stable_ms": r4(torch_ms),
+        "torch_over_argsort": r4(torch_ms / argsort_ms),
+        "exact_vs_torch_sort_stable": exact,
+        "streaming": {
+            "pack": {"bytes": 12 * n, "gb_per_s": r4(gbs(12 * n, pack_ms)), "memcpy_ms": r4(copies["pack"]),
+                     "memcpy_gb_per_s": r4(gbs(12 * n, copies["pack"])), "frac_of_memcpy": r4(copies["pack"] / pack_ms)},
+            "unpack": {"bytes": 16 * n, "gb_per_s": r4(gbs(16 * n, unpack_ms)), "memcpy_ms": r4(copies["unpack"]),
+                       "memcpy_gb_per_s": r4(gbs(16 * n, copies["unpack"])),
+                       "frac_of_memcpy": r4(copies["unpack"] / unpack_ms)},
+        },
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--log2", type=int, nargs="+", default=[28, 30])
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "pairs_bench.json"))
+    args = ap.parse_args()
+
+    import torch
+
+    import dsort
+
+    if not torch.cuda.is_available():
+        sys.exit("bench_pairs: no GPU visible (nothing is measured without one)")
+    ctx = dsort.Context(0)
+    res = {"what": "stable argsort of uniform int32 keys, resident in HBM (dsort_argsort_dev_i32)",
+           "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup,
+           "sizes": [bench_size(torch, ctx, 1 << lg, args.steps, args.warmup) for lg in args.log2]}
+    ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"pairs_bench": [{"n": s["n"], "argsort_ms": s["argsort_ms"], "legs_ms": s["legs_ms"],
+                                       "torch_sort_stable_ms": s["torch_sort_stable_ms"],
+                                       "torch_over_argsort": s["torch_over_argsort"],
+                                       "pack_frac_of_memcpy": s["streaming"]["pack"]["frac_of_memcpy"],
+                                       "unpack_frac_of_memcpy": s["streaming"]["unpack"]["frac_of_memcpy"],
+                                       "exact": s["exact_vs_torch_sort_stable"]} for s in res["sizes"]]}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
