@@ -1125,6 +1125,13 @@ static int sample_sort_entry(dsort_ctx *ctx, const T *d, size_t n, T **o, size_t
     return rc;
 }
 
+namespace dsort {
+int sample_sort_packed(dsort_ctx *ctx, const int64_t *d_in, size_t n_local, int64_t **d_out, size_t *n_out,
+                       void *stream) {
+    return sample_sort_entry<int64_t>(ctx, d_in, n_local, d_out, n_out, stream, false);
+}
+}  // namespace dsort
+
 extern "C" {
 
 const char *dsort_version(void) { return DSORT_VERSION_STRING; }
@@ -1173,7 +1180,8 @@ int dsort_finalize(dsort_ctx *ctx) {
     flush_later(ctx);
     void *bufs[] = {ctx->scratch, ctx->scratch2, ctx->splits, ctx->groups, ctx->io, ctx->io2, ctx->red,
                     ctx->local, ctx->recv, ctx->recv2, ctx->small, ctx->text_status,
-                    ctx->bucket, ctx->sub, ctx->sub_alt, ctx->stmp, ctx->bxs, ctx->tfb, ctx->fence, ctx->pairs};
+                    ctx->bucket, ctx->sub, ctx->sub_alt, ctx->stmp, ctx->bxs, ctx->tfb, ctx->fence, ctx->pairs,
+                    ctx->spairs_k, ctx->spairs_v};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->red_host) (void)hipHostFree(ctx->red_host);

@@ -104,6 +104,10 @@ struct dsort_ctx {
     size_t pairs_bytes = 0;
     hipEvent_t pairs_ev[4] = {};  // around its pack, sort and unpack legs (created on first use)
     bool pairs_ev_ok = false;     // ... all four recorded by the last pair sort
+    void *spairs_k = nullptr;     // the pair sample sort's slice, unpacked: sorted keys (4 B each) ...
+    size_t spairs_k_bytes = 0;
+    void *spairs_v = nullptr;     // ... and their indices / values
+    size_t spairs_v_bytes = 0;
     void *bucket = nullptr;       // partition pass of the bucketed int32 sort (dsort_bucket.h)
     size_t bucket_bytes = 0;
     void *bucket_host = nullptr;  // pinned: bucket starts
@@ -250,6 +254,10 @@ int sort_stages(const dsort_opts &opt, uint64_t n, int key_bytes);
 // arena around them (the pair sort) brackets its whole sequence as well.
 int order_begin(dsort_ctx *ctx, hipStream_t s);
 int order_end(dsort_ctx *ctx, hipStream_t s);
+// dsort_sample_sort_dev_i64 for the pair sample sort (dsort_pairs.hip; the sample sort is static in
+// dsort_api.hip).  Takes the comm mutex itself: the caller must not hold it.
+int sample_sort_packed(dsort_ctx *ctx, const int64_t *d_in, size_t n_local, int64_t **d_out, size_t *n_out,
+                       void *stream);
 // Host waits of the sort: blocking, or (ctx->poll_waits) polling with the abort flag and deadline
 // (DSORT_ECOMM / DSORT_ETIMEOUT).
 int sync_event(dsort_ctx *ctx, hipEvent_t e, const char *what);

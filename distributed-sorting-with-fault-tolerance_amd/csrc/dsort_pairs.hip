@@ -6,7 +6,8 @@
 // (sort_device<int64_t>, untouched: every packed word of an argsort is distinct, which is the
 // input the int64 sort has the least to say about), unpack.  With value = input position the
 // order is the stable argsort.  Records wider than 32 bits follow their key by an argsort and a
-// gather (gather_kernel).
+// gather (gather_kernel).  Across ranks the packed words go through the int64 sample sort instead
+// (sample_pairs_sort, ABI 8), the argsort's value being the global position.
 //
 // The three kernels are streaming: grid-stride, 16 bytes per store and, but for the pack's keys
 // and values, per load; outputs as non-temporal stores.  The caller's pointers are only
@@ -45,7 +46,8 @@ __device__ __forceinline__ uint64_t pack1(int32_t k, uint32_t v) {
 // 8 bytes of caller memory
 typedef uint32_t u2_a4 __attribute__((ext_vector_type(2), aligned(4)));
 
-// packed[i] = keys[i] : (ARG ? i : vals[i]).  A wave takes 256 elements, lane l the pairs at 2l
+// packed[i] = keys[i] : (ARG ? (uint32_t)(base + i) : vals[i]); base is the global position of
+// keys[0] in a sample argsort, 0 in a local one.  A wave takes 256 elements, lane l the pairs at 2l
 // and at 128 + 2l: each of its two 16-byte stores is then contiguous over the wave (1 KiB), at the
 // price of 8-byte loads.  (Four consecutive elements per lane -- one 16-byte key load, two stores
 // 32 bytes apart, so that every store instruction fills half of each line it touches -- measured
@@ -54,7 +56,8 @@ typedef uint32_t u2_a4 __attribute__((ext_vector_type(2), aligned(4)));
 template <bool ARG>
 __global__ void __launch_bounds__(NT) pairs_pack_kernel(const int32_t *__restrict__ keys,
                                                         const uint32_t *__restrict__ vals,
-                                                        uint64_t *__restrict__ packed, uint64_t n) {
+                                                        uint64_t *__restrict__ packed, uint64_t n,
+                                                        uint32_t base) {
     const uint64_t chunks = n >> 8;
     const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
     const uint64_t nwaves = ((uint64_t)gridDim.x * NT) >> 6;
@@ -65,8 +68,8 @@ __global__ void __launch_bounds__(NT) pairs_pack_kernel(const int32_t *__restric
         const u2_a4 k1 = *reinterpret_cast<const u2_a4 *>(keys + e1);
         u2_a4 v0, v1;
         if (ARG) {
-            v0 = u2_a4{(uint32_t)e0, (uint32_t)e0 + 1};
-            v1 = u2_a4{(uint32_t)e1, (uint32_t)e1 + 1};
+            v0 = u2_a4{base + (uint32_t)e0, base + (uint32_t)e0 + 1};
+            v1 = u2_a4{base + (uint32_t)e1, base + (uint32_t)e1 + 1};
         } else {
             v0 = *reinterpret_cast<const u2_a4 *>(vals + e0);
             v1 = *reinterpret_cast<const u2_a4 *>(vals + e1);
@@ -77,7 +80,7 @@ __global__ void __launch_bounds__(NT) pairs_pack_kernel(const int32_t *__restric
                                     reinterpret_cast<l2 *>(packed + e1));
     }
     const uint64_t i = (chunks << 8) + t;  // the n % 256 last elements, one each
-    if (i < n) packed[i] = pack1(keys[i], ARG ? (uint32_t)i : vals[i]);
+    if (i < n) packed[i] = pack1(keys[i], ARG ? base + (uint32_t)i : vals[i]);
 }
 
 // keys_out[i] = high word, vals_out[i] = low word of packed[i]; a NULL output is not written
@@ -151,6 +154,19 @@ static bool leg_event(dsort_ctx *ctx, int i, hipStream_t s) {
     return hipEventRecord(ctx->pairs_ev[i], s) == hipSuccess;
 }
 
+static int pack(dsort_ctx *ctx, const int32_t *keys_in, const uint32_t *vals_in, uint64_t *packed, size_t n,
+                uint32_t base, hipStream_t s) {
+    const unsigned grid = grid_for((n + 3) / 4);
+    if (vals_in)
+        hipLaunchKernelGGL((pairs_pack_kernel<false>), dim3(grid), dim3(NT), 0, s, keys_in, vals_in, packed,
+                           (uint64_t)n, base);
+    else
+        hipLaunchKernelGGL((pairs_pack_kernel<true>), dim3(grid), dim3(NT), 0, s, keys_in, vals_in, packed,
+                           (uint64_t)n, base);
+    DSORT_HIP(ctx, hipGetLastError());
+    return DSORT_OK;
+}
+
 // Sorts (keys_in[i], vals_in ? vals_in[i] : i) by key, then by value as unsigned 32-bit, into
 // keys_out / vals_out (either may be NULL: not wanted; either may be its input: the pack has
 // consumed the inputs before the unpack writes).  Asynchronous on s.
@@ -172,13 +188,8 @@ static int pairs_sort(dsort_ctx *ctx, const int32_t *keys_in, const uint32_t *va
     uint64_t *packed = static_cast<uint64_t *>(ctx->pairs);
     ctx->pairs_ev_ok = leg_event(ctx, 0, s);
     const unsigned grid = grid_for((n + 3) / 4);
-    if (vals_in)
-        hipLaunchKernelGGL((pairs_pack_kernel<false>), dim3(grid), dim3(NT), 0, s, keys_in, vals_in, packed,
-                           (uint64_t)n);
-    else
-        hipLaunchKernelGGL((pairs_pack_kernel<true>), dim3(grid), dim3(NT), 0, s, keys_in, vals_in, packed,
-                           (uint64_t)n);
-    DSORT_HIP(ctx, hipGetLastError());
+    rc = pack(ctx, keys_in, vals_in, packed, n, 0, s);
+    if (rc) return rc;
     ctx->pairs_ev_ok = ctx->pairs_ev_ok && leg_event(ctx, 1, s);
     // DSORT_OPT_KILL_AFTER_STAGE fires inside, as for any int64 sort of n keys; DSORT_ESTAGE (the
     // stage was never reached) leaves a valid output, so the unpack still runs
@@ -191,6 +202,61 @@ static int pairs_sort(dsort_ctx *ctx, const int32_t *keys_in, const uint32_t *va
     ctx->pairs_ev_ok = ctx->pairs_ev_ok && leg_event(ctx, 3, s);
     rc = order_end(ctx, s);
     return rc ? rc : src;
+}
+
+// The pair sort across ranks: the packed words go through the int64 sample sort (both exchange
+// paths, both transports, untouched) and this rank's slice is unpacked into two arenas of the
+// context.  The words of an argsort are all distinct -- base = the global position of keys_in[0] --
+// so a heavy key splits between ranks by position and the global order is stable.
+//
+// The slice the sample sort returns starts at the base of its output arena on both exchange paths
+// (ctx->recv2, a hipMalloc of its own: 256-byte aligned), which is what the unpack's 16-byte loads
+// need; checked below, since that is the sample sort's business and may change.
+//
+// The pair arena is the sample sort's input: read on s, and by the comm stream of the RCCL bucket
+// exchange, which starts behind an event of s and which the sample sort has waited for when it
+// returns 0.  One order bracket around the three legs, as in pairs_sort.  The sample sort takes the
+// comm mutex itself (not recursive): nothing here holds it.
+//
+// A rank without keys (n == 0) packs nothing and joins every collective of the sample sort.
+static int sample_pairs_sort(dsort_ctx *ctx, const int32_t *keys_in, const uint32_t *vals_in, uint32_t base, size_t n,
+                             int32_t **keys_out, uint32_t **vals_out, size_t *n_out, void *stream) {
+    if (n > SIZE_MAX / 8) return set_err(ctx, DSORT_EINVAL, "pair sample sort: n * 8 bytes overflow size_t");
+    hipStream_t s = pick_stream(ctx, stream);
+    int rc = order_begin(ctx, s);
+    if (rc) return rc;
+    rc = ensure(ctx, &ctx->pairs, &ctx->pairs_bytes, (n ? n : 1) * 8, "pair arena");
+    if (rc) return rc;
+    uint64_t *packed = static_cast<uint64_t *>(ctx->pairs);
+    ctx->pairs_ev_ok = leg_event(ctx, 0, s);
+    if (n && (rc = pack(ctx, keys_in, vals_in, packed, n, base, s))) return rc;
+    ctx->pairs_ev_ok = ctx->pairs_ev_ok && leg_event(ctx, 1, s);
+    int64_t *slice = nullptr;
+    size_t m = 0;
+    rc = sample_sort_packed(ctx, reinterpret_cast<const int64_t *>(packed), n, &slice, &m, stream);
+    if (rc) return rc;
+    if (m && (reinterpret_cast<uintptr_t>(slice) & 15))
+        return set_err(ctx, DSORT_EHIP, "pair sample sort: the sample sort's slice is not 16-byte aligned");
+    if (keys_out) {
+        rc = ensure(ctx, &ctx->spairs_k, &ctx->spairs_k_bytes, (m ? m : 1) * 4, "pair sample sort keys");
+        if (rc) return rc;
+    }
+    rc = ensure(ctx, &ctx->spairs_v, &ctx->spairs_v_bytes, (m ? m : 1) * 4, "pair sample sort values");
+    if (rc) return rc;
+    int32_t *ko = keys_out ? static_cast<int32_t *>(ctx->spairs_k) : nullptr;
+    uint32_t *vo = static_cast<uint32_t *>(ctx->spairs_v);
+    ctx->pairs_ev_ok = ctx->pairs_ev_ok && leg_event(ctx, 2, s);
+    if (m) {
+        hipLaunchKernelGGL(pairs_unpack_kernel, dim3(grid_for((m + 3) / 4)), dim3(NT), 0, s,
+                           reinterpret_cast<const uint64_t *>(slice), ko, vo, (uint64_t)m);
+        DSORT_HIP(ctx, hipGetLastError());
+    }
+    ctx->pairs_ev_ok = ctx->pairs_ev_ok && leg_event(ctx, 3, s);
+    if ((rc = order_end(ctx, s))) return rc;
+    if (keys_out) *keys_out = ko;
+    *vals_out = vo;
+    *n_out = m;
+    return DSORT_OK;
 }
 
 }  // namespace pr
@@ -214,6 +280,23 @@ int dsort_sort_pairs_dev_i32(dsort_ctx *ctx, const int32_t *d_keys_in, const uin
     if (!ctx) return DSORT_EINVAL;
     if (n && (!d_keys_in || !d_vals_in || !d_vals_out)) return set_err(ctx, DSORT_EINVAL, "null argument");
     return pr::pairs_sort(ctx, d_keys_in, d_vals_in, d_keys_out, d_vals_out, n, pick_stream(ctx, stream));
+}
+
+int dsort_sample_argsort_dev_i32(dsort_ctx *ctx, const int32_t *d_keys, size_t n_local, uint64_t first,
+                                 int32_t **d_keys_out, uint32_t **d_idx_out, size_t *n_out, void *stream) {
+    if (!ctx) return DSORT_EINVAL;
+    if (first > (1ull << 32) || (uint64_t)n_local > (1ull << 32) - first)
+        return set_err(ctx, DSORT_EINVAL,
+                       "sample argsort: first + n_local exceeds 2^32 (a global position must fit 32 bits)");
+    if (!d_idx_out || !n_out || (n_local && !d_keys)) return set_err(ctx, DSORT_EINVAL, "null argument");
+    return pr::sample_pairs_sort(ctx, d_keys, nullptr, (uint32_t)first, n_local, d_keys_out, d_idx_out, n_out, stream);
+}
+
+int dsort_sample_sort_pairs_dev_i32(dsort_ctx *ctx, const int32_t *d_keys, const uint32_t *d_vals, size_t n_local,
+                                    int32_t **d_keys_out, uint32_t **d_vals_out, size_t *n_out, void *stream) {
+    if (!ctx) return DSORT_EINVAL;
+    if (!d_vals_out || !n_out || (n_local && (!d_keys || !d_vals))) return set_err(ctx, DSORT_EINVAL, "null argument");
+    return pr::sample_pairs_sort(ctx, d_keys, d_vals, 0, n_local, d_keys_out, d_vals_out, n_out, stream);
 }
 
 int dsort_gather_dev(dsort_ctx *ctx, const void *d_src, const uint32_t *d_idx, void *d_dst, size_t n, int elem_bytes,
@@ -260,7 +343,8 @@ int dsort_argsort_i32(dsort_ctx *ctx, const int32_t *keys, int32_t *keys_out, ui
 }
 
 // Not part of the ABI (like dsort_debug_stamps): device time of the last pair sort's three legs
-// -- pack, int64 sort, unpack -- from HIP events between them, for scripts/bench_pairs.py.
+// -- pack, int64 sort (a pair sample sort: the whole sample sort, its host waits included), unpack
+// -- from HIP events between them, for scripts/bench_pairs.py.
 // Blocks until that call has finished; DSORT_EINVAL when it recorded none (no pair sort yet, or
 // DSORT_OPT_STAGE_TIMING off).
 int dsort_pairs_leg_ms(dsort_ctx *ctx, double ms[3]) {

@@ -44,6 +44,7 @@ EXPORTS = [
     "dsort_host_unregister", "dsort_write_text_i32", "dsort_format_text_dev_i32",
     "dsort_parse_text_dev_i32", "dsort_parse_text_i32", "dsort_format_text_i32",
     "dsort_argsort_dev_i32", "dsort_sort_pairs_dev_i32", "dsort_gather_dev", "dsort_argsort_i32",
+    "dsort_sample_argsort_dev_i32", "dsort_sample_sort_pairs_dev_i32",
 ]
 
 
@@ -260,6 +261,10 @@ def load():
         "dsort_sort_pairs_dev_i32": (ctypes.c_int, [P, P, P, P, P, SZ, P]),
         "dsort_gather_dev": (ctypes.c_int, [P, P, P, P, SZ, ctypes.c_int, P]),
         "dsort_argsort_i32": (ctypes.c_int, [P, P, P, P, SZ]),
+        "dsort_sample_argsort_dev_i32": (ctypes.c_int, [P, P, SZ, U64, ctypes.POINTER(P), ctypes.POINTER(P),
+                                                        ctypes.POINTER(SZ), P]),
+        "dsort_sample_sort_pairs_dev_i32": (ctypes.c_int, [P, P, P, SZ, ctypes.POINTER(P), ctypes.POINTER(P),
+                                                           ctypes.POINTER(SZ), P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -634,6 +639,46 @@ class Context:
                                                                        ctypes.byref(outp), ctypes.byref(nout),
                                                                        self._stream()))
         return outp.value or 0, nout.value
+
+    # ---------------- argsort and key-value sort across ranks (int32 keys; dsort.h, ABI 8) ----
+    def _slices(self, ptrs, n, device):
+        """Fresh int32 tensors holding the context-owned slices at `ptrs` (n elements each).  The
+        unpack that fills them was queued on torch's current stream and dsort_copy_d2d runs on the
+        context's: the stream is drained first."""
+        torch.cuda.current_stream().synchronize()
+        outs = []
+        for p in ptrs:
+            t = torch.empty(n, dtype=torch.int32, device=device)
+            if n:
+                self.check(self.lib.dsort_copy_d2d(self.h, t.data_ptr(), p.value, 4 * n))
+            outs.append(t)
+        return outs
+
+    def sample_argsort_dev(self, keys, first):
+        """Global stable argsort over the communicator (dsort_sample_argsort_dev_i32): `keys` is
+        this rank's chunk, holding the global positions first .. first + len(keys) - 1.  Returns
+        (sorted_keys, idx), this rank's slice of the global order as fresh int32 CUDA tensors; idx
+        holds global positions as uint32 bit patterns, as argsort_dev documents."""
+        n = self._i32(keys, "keys").numel()
+        kp, ip, nout = P(), P(), SZ()
+        self.check(self.lib.dsort_sample_argsort_dev_i32(self.h, keys.data_ptr() if n else None, n, int(first),
+                                                         ctypes.byref(kp), ctypes.byref(ip), ctypes.byref(nout),
+                                                         self._stream()))
+        k, i = self._slices((kp, ip), nout.value, keys.device)
+        return k, i
+
+    def sample_sort_pairs_dev(self, keys, vals):
+        """Global key-value sort over the communicator (dsort_sample_sort_pairs_dev_i32): ascending
+        by key, equal keys by value as UNSIGNED 32-bit.  Returns (sorted_keys, sorted_vals), this
+        rank's slice as fresh int32 CUDA tensors (the values as uint32 bit patterns)."""
+        n = self._i32(keys, "keys").numel()
+        self._i32(vals, "vals", n)
+        kp, vp, nout = P(), P(), SZ()
+        self.check(self.lib.dsort_sample_sort_pairs_dev_i32(self.h, keys.data_ptr() if n else None,
+                                                            vals.data_ptr() if n else None, n, ctypes.byref(kp),
+                                                            ctypes.byref(vp), ctypes.byref(nout), self._stream()))
+        k, v = self._slices((kp, vp), nout.value, keys.device)
+        return k, v
 
     def copy_d2h(self, host, dptr, nbytes):
         self.check(self.lib.dsort_copy_d2h(self.h, _ptr(host), dptr, nbytes))

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DSORT_ABI_VERSION 7
+#define DSORT_ABI_VERSION 8
 
 #define DSORT_OK 0
 #define DSORT_EINVAL (-1)   /* bad argument */
@@ -313,6 +313,50 @@ int dsort_sample_merge_dev_i32(dsort_ctx *ctx, const int32_t *d_sorted, size_t n
                                int32_t **d_out, size_t *n_out, void *stream);
 int dsort_sample_merge_dev_i64(dsort_ctx *ctx, const int64_t *d_sorted, size_t n_local,
                                int64_t **d_out, size_t *n_out, void *stream);
+
+/* ABI 8: the argsort and the key-value sort of int32 keys (ABI 7) across the ranks of the
+ * communicator.  Every rank packs its chunk into the context's pair arena as for the local pair
+ * sort -- (int64)key << 32 | (uint32)value, the value of the argsort being the key's GLOBAL position
+ * -- and the packed words go through the int64 sample sort, whichever exchange path and transport it
+ * takes; the rank's slice is then unpacked into two arrays of the context.  The packed words of an
+ * argsort are all distinct, so a heavy key is split between ranks by position and the global order
+ * is stable.
+ *
+ * Contract, as for dsort_sample_sort_dev_*: the inputs are not modified; on return *n_out is this
+ * rank's slice length and *d_keys_out, *d_idx_out / *d_vals_out point to context-owned arrays of
+ * *n_out elements, valid until the next sample sort or pair call on this context or
+ * dsort_finalize.  The unpack is queued on `stream`: the arrays are ready after the stream.
+ * d_keys_out == NULL: the sorted keys are not wanted.  Concatenating the slices of ranks
+ * 0..nranks-1 gives the global order -- argsort: ascending by key, equal keys in ascending global
+ * position (stable); pairs: ascending by key, equal keys by value as UNSIGNED 32-bit.  A rank with
+ * n_local == 0 (its inputs may be NULL) still takes part in every collective.
+ *
+ * Errors (DSORT_ECOMM / DSORT_ETIMEOUT and the status gates of the host transport included),
+ * DSORT_OPT_KILL_AFTER_STAGE -- with dsort_sample_sort_stages(.., key_bytes = 8, ..) -- and
+ * dsort_get_stats behave as on dsort_sample_sort_dev_i64 of the same key counts.  An argument
+ * error, or a failure to allocate the pair arena, returns before the first collective, as a NULL
+ * argument of dsort_sample_sort_dev_* does.
+ *
+ * Memory: the pair arena (8 * n_local bytes) and 8 * n_out bytes of output arrays (4 * n_out
+ * without the keys), all grow-only, on top of the int64 sample sort's memory for these counts.
+ *
+ * Not offered: delivering wider payload records to the rank that holds their key (a distributed
+ * gather needs an exchange of its own; on one rank dsort_gather_dev applies the indices as
+ * before); int64 keys with a payload; the presorted / fault-survivor entry
+ * (dsort_sample_merge_dev_*) for pairs; the C master and workers, which move bare keys. */
+
+/* Global stable argsort.  The rank's chunk d_keys[0..n_local) holds the global positions
+ * first .. first + n_local - 1 (`first` as in dsort_gen_uniform_*); (*d_idx_out)[j] is the global
+ * position of the j-th key of this rank's slice.  first + n_local > 2^32 returns DSORT_EINVAL
+ * before any memory or collective is touched; ranks passing overlapping ranges is the caller's
+ * error (not checked). */
+int dsort_sample_argsort_dev_i32(dsort_ctx *ctx, const int32_t *d_keys, size_t n_local, uint64_t first,
+                                 int32_t **d_keys_out, uint32_t **d_idx_out, size_t *n_out,
+                                 void *stream);
+/* Global key-value sort.  No bound on the counts beyond memory. */
+int dsort_sample_sort_pairs_dev_i32(dsort_ctx *ctx, const int32_t *d_keys, const uint32_t *d_vals,
+                                    size_t n_local, int32_t **d_keys_out, uint32_t **d_vals_out,
+                                    size_t *n_out, void *stream);
 
 /* ---------------------------------------------------------------- sample-sort planning  */
 /* Host-side planning rules of the sample sort, exported so that the CPU tests (gloo, no GPU)

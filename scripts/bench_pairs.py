@@ -15,6 +15,13 @@ For uniform keys at every --log2 size (default 2^28 and 2^30):
 
     python scripts/bench_pairs.py [--log2 28 30] [--steps 10] [--warmup 2] [--out profiles/pairs_bench.json]
 
+    python scripts/bench_pairs.py --sample [--log2 28] [--steps 10] [--out profiles/pairs_sample_bench.json]
+
+--sample measures instead the global argsort (dsort_sample_argsort_dev_i32) on one RCCL rank: ms per
+call of --steps back-to-back calls, its pack / sample sort / unpack legs from the same HIP events,
+and dsort_argsort_dev_i32 with its legs on the same keys in the same process; it reports the ratio
+and the excess leg by leg (bench_sample).
+
 Writes the JSON file and prints one summary line.  No GPU: fails (there is nothing to measure).
 """
 import argparse
@@ -101,13 +108,82 @@ def bench_size(torch, ctx, n, steps, warmup):
     }
 
 
+def bench_sample(torch, dsort, ctx, n, steps, warmup):
+    """--sample: dsort_sample_argsort_dev_i32 on ONE RCCL rank against dsort_argsort_dev_i32 on the
+    same keys in the same process.  One rank ships nothing: what is measured is the sample sort's
+    own route for the packed words (at 2^22 keys and more the bucket exchange: samples, first
+    partition level, second level and tile sort wave by wave, with its host waits) against the
+    local int64 sort, plus the two streaming legs."""
+    ctx.comm_init(1, 0, dsort.Context.unique_id())
+    keys = torch.empty(n, dtype=torch.int32, device="cuda")
+    ctx.gen_uniform(keys, 0x5EED2026, 0)
+    out = torch.empty_like(keys)
+    idx = torch.empty_like(keys)
+    leg_fn = ctx.lib.dsort_pairs_leg_ms  # not in dsort.h: the bench's view of the legs' events
+    leg_fn.restype = ctypes.c_int
+    leg_fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+
+    def legs_of(fn):
+        legs = []
+        for _ in range(steps):
+            fn()
+            ms = (ctypes.c_double * 3)()
+            ctx.check(leg_fn(ctx.h, ms))
+            legs.append(tuple(ms))
+        return [round(statistics.median(x[i] for x in legs), 4) for i in range(3)]
+
+    kp, ip, nout = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+
+    def sample():  # the C entry itself: the binding's copies into fresh tensors are not part of it
+        ctx.check(ctx.lib.dsort_sample_argsort_dev_i32(ctx.h, keys.data_ptr(), n, 0, ctypes.byref(kp),
+                                                       ctypes.byref(ip), ctypes.byref(nout), ctx._stream()))
+
+    def local():
+        ctx.argsort_dev(keys, idx_out=idx, keys_out=out)
+
+    local_ms = timed(torch, local, steps, warmup)
+    local_legs = legs_of(local)
+    local_stats = ctx.stats()
+    sample_ms = timed(torch, sample, steps, warmup)
+    sample_legs = legs_of(sample)
+    st = ctx.stats()
+    sk, si = ctx.sample_argsort_dev(keys, 0)  # (the check, through the binding)
+    local()
+    torch.cuda.synchronize()
+    exact = bool(sk.numel() == n and torch.equal(sk, out) and torch.equal(si, idx))
+    ctx.comm_destroy()
+    r4 = lambda x: round(x, 4)  # noqa: E731
+    names = ("pack", "sort", "unpack")
+    return {
+        "n": n,
+        "sample_argsort_ms": r4(sample_ms),
+        "local_argsort_ms": r4(local_ms),
+        "sample_over_local": r4(sample_ms / local_ms),
+        "sample_legs_ms": dict(zip(names, sample_legs)),
+        "local_legs_ms": dict(zip(names, local_legs)),
+        "excess_ms_by_leg": {k: r4(a - b) for k, a, b in zip(names, sample_legs, local_legs)},
+        "sample_sort_stats": {k: st[k] for k in ("exchange_path", "total_ms", "partition_ms", "bucket_hist_ms",
+                                                 "bucket_scatter_ms", "sub_partition_ms", "tile_sort_kernel_ms",
+                                                 "exchange_ms", "alltoall_ms", "keys_sent", "keys_out")},
+        "local_sort_stats": {k: local_stats[k] for k in ("total_ms", "partition_ms", "bucket_hist_ms",
+                                                         "bucket_scatter_ms", "sub_partition_ms",
+                                                         "tile_sort_kernel_ms")},
+        "exact_vs_local_argsort": exact,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--log2", type=int, nargs="+", default=[28, 30])
+    ap.add_argument("--log2", type=int, nargs="+", default=None)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "pairs_bench.json"))
+    ap.add_argument("--sample", action="store_true",
+                    help="time dsort_sample_argsort_dev_i32 on one RCCL rank against the local argsort "
+                         "(default 2^28 keys, profiles/pairs_sample_bench.json)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.log2 = args.log2 or ([28] if args.sample else [28, 30])
+    args.out = args.out or os.path.join(REPO, "profiles", "pairs_sample_bench.json" if args.sample else "pairs_bench.json")
 
     import torch
 
@@ -116,6 +192,22 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_pairs: no GPU visible (nothing is measured without one)")
     ctx = dsort.Context(0)
+    if args.sample:
+        res = {"what": "global stable argsort of uniform int32 keys on one RCCL rank (dsort_sample_argsort_dev_i32) "
+                       "against dsort_argsort_dev_i32 of the same resident keys, same process; ms per call of "
+                       "--steps back-to-back calls, legs from the HIP events between them (median)",
+               "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup,
+               "sizes": [bench_sample(torch, dsort, ctx, 1 << lg, args.steps, args.warmup) for lg in args.log2]}
+        ctx.close()
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"pairs_sample_bench": [{k: s[k] for k in ("n", "sample_argsort_ms", "local_argsort_ms",
+                                                                    "sample_over_local", "sample_legs_ms",
+                                                                    "local_legs_ms", "exact_vs_local_argsort")}
+                                                 for s in res["sizes"]]}), flush=True)
+        return
     res = {"what": "stable argsort of uniform int32 keys, resident in HBM (dsort_argsort_dev_i32)",
            "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup,
            "sizes": [bench_size(torch, ctx, 1 << lg, args.steps, args.warmup) for lg in args.log2]}
