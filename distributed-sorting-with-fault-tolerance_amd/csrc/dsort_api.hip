@@ -96,7 +96,7 @@ void flush_later(dsort_ctx *ctx) {
 }
 
 // grow-only pinned host buffer
-static int ensure_host(dsort_ctx *ctx, void **buf, size_t *have, size_t need) {
+int ensure_host(dsort_ctx *ctx, void **buf, size_t *have, size_t need) {
     if (need <= *have && *buf) return DSORT_OK;
     if (*buf) release_host(ctx, *buf);
     *buf = nullptr;
@@ -388,7 +388,7 @@ static double now_ms() {
 // dsort_comm_abort from another thread finds it taken and only raises ctx->abort_req (dsort.h).
 static std::mutex &comm_mutex(dsort_ctx *ctx) { return ctx->comm_mu; }
 
-static void abort_comm_locked(dsort_ctx *ctx) {
+void abort_comm_locked(dsort_ctx *ctx) {
     if (ctx->comm) ncclCommAbort(ctx->comm);
     ctx->comm = nullptr;
     ctx->has_transport = false;
@@ -401,8 +401,7 @@ static void abort_comm_locked(dsort_ctx *ctx) {
 // instead of a hipStreamSynchronize that a dead peer would block forever.
 // hold (DSORT_OPT_TEST_HOLD_EXCHANGE): the wait reports "not done" as if a peer never sent, until
 // the abort flag or the deadline ends it.
-static int exch_wait(dsort_ctx *ctx, hipStream_t s, bool with_stream, double deadline, const char *what,
-                     bool hold = false) {
+int exch_wait(dsort_ctx *ctx, hipStream_t s, bool with_stream, double deadline, const char *what, bool hold) {
     PollPause pause;
     for (;;) {
         const hipError_t q0 = with_stream ? hipStreamQuery(s) : hipSuccess;
@@ -447,7 +446,7 @@ static void exchange_fault_point(dsort_ctx *ctx, int stage) {
 // DSORT_OPT_TEST_FAIL_EXCHANGE = k (host transport): a local error of this rank right before its
 // k-th collective (0 = the key-count all-gather), returned like any other local error -- the
 // sequence's guard reports it to the peers at the next gate (dsort_tx.h)
-static int tx_fault_point(dsort_ctx *ctx) {
+int tx_fault_point(dsort_ctx *ctx) {
     if (ctx->tx && ctx->opt.test_fail_exchange >= 0 && ctx->opt.test_fail_exchange == ctx->tx->collectives_done())
         return set_err(ctx, DSORT_EHIP, "injected local failure before collective " +
                                             std::to_string(ctx->opt.test_fail_exchange) +
@@ -457,8 +456,8 @@ static int tx_fault_point(dsort_ctx *ctx) {
 
 // All-gather of `count` uint64 per rank (RCCL through the context's small device buffer, or the
 // host transport): out[r * count + i] = rank r's src[i].
-static int allgather_u64(dsort_ctx *ctx, const uint64_t *src, size_t count, uint64_t *out, hipStream_t s,
-                         double deadline, const char *what) {
+int allgather_u64(dsort_ctx *ctx, const uint64_t *src, size_t count, uint64_t *out, hipStream_t s, double deadline,
+                  const char *what) {
     const int P = ctx->nranks;
     if (ctx->has_transport) {
         if (!ctx->tx) return set_err(ctx, DSORT_EINVAL, std::string(what) + ": no sample sort running");
@@ -1181,11 +1180,15 @@ int dsort_finalize(dsort_ctx *ctx) {
     void *bufs[] = {ctx->scratch, ctx->scratch2, ctx->splits, ctx->groups, ctx->io, ctx->io2, ctx->red,
                     ctx->local, ctx->recv, ctx->recv2, ctx->small, ctx->text_status,
                     ctx->bucket, ctx->sub, ctx->sub_alt, ctx->stmp, ctx->bxs, ctx->tfb, ctx->fence, ctx->pairs,
-                    ctx->spairs_k, ctx->spairs_v};
+                    ctx->spairs_k, ctx->spairs_v, ctx->gat_req, ctx->gat_rreq, ctx->gat_rep, ctx->gat_back,
+                    ctx->gat_small};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->red_host) (void)hipHostFree(ctx->red_host);
     if (ctx->small_host) (void)hipHostFree(ctx->small_host);
+    if (ctx->gat_host) (void)hipHostFree(ctx->gat_host);
+    for (auto &e : ctx->gat_ev)
+        if (e) (void)hipEventDestroy(e);
     if (ctx->xfer) (void)hipHostFree(ctx->xfer);
     if (ctx->xfer2) (void)hipHostFree(ctx->xfer2);
     if (ctx->fence_host) (void)hipHostFree(ctx->fence_host);

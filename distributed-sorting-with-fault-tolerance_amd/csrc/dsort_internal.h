@@ -108,6 +108,22 @@ struct dsort_ctx {
     size_t spairs_k_bytes = 0;
     void *spairs_v = nullptr;     // ... and their indices / values
     size_t spairs_v_bytes = 0;
+    // the distributed gather (dsort_gather.hip): arenas of its own, so that a gather leaves the
+    // slices of the preceding sample sort / argsort (recv2, spairs_k, spairs_v) alone
+    void *gat_req = nullptr;      // this rank's requests, owner-major (4 B per index)
+    size_t gat_req_bytes = 0;
+    void *gat_rreq = nullptr;     // the requests received (4 B each)
+    size_t gat_rreq_bytes = 0;
+    void *gat_rep = nullptr;      // the records served (W bytes per request received)
+    size_t gat_rep_bytes = 0;
+    void *gat_back = nullptr;     // the records that came back (W bytes per index)
+    size_t gat_back_bytes = 0;
+    void *gat_small = nullptr;    // owner table, per-workgroup counts, bin starts and totals
+    size_t gat_small_bytes = 0;
+    void *gat_host = nullptr;     // pinned: the owner table and the bin totals
+    size_t gat_host_bytes = 0;
+    hipEvent_t gat_ev[6] = {};    // around its five legs (created on first use)
+    bool gat_ev_ok = false;       // ... all six recorded by the last gather
     void *bucket = nullptr;       // partition pass of the bucketed int32 sort (dsort_bucket.h)
     size_t bucket_bytes = 0;
     void *bucket_host = nullptr;  // pinned: bucket starts
@@ -271,6 +287,18 @@ struct PollPause {
     double t0 = -1.0;
     void operator()();
 };
+// Pieces of the sample sort's exchange (dsort_api.hip) that the distributed gather
+// (dsort_gather.hip) drives its own collectives with.  abort_comm_locked: the caller holds
+// ctx->comm_mu.  exch_wait: every wait of an exchange (stream, RCCL's asynchronous error, abort flag,
+// deadline).  tx_fault_point: DSORT_OPT_TEST_FAIL_EXCHANGE.  allgather_u64: `count` uint64 per rank
+// over either transport (the host transport's through ctx->tx, fault point included).
+void abort_comm_locked(dsort_ctx *ctx);
+int exch_wait(dsort_ctx *ctx, hipStream_t s, bool with_stream, double deadline, const char *what,
+              bool hold = false);
+int tx_fault_point(dsort_ctx *ctx);
+int allgather_u64(dsort_ctx *ctx, const uint64_t *src, size_t count, uint64_t *out, hipStream_t s,
+                  double deadline, const char *what);
+int ensure_host(dsort_ctx *ctx, void **buf, size_t *have, size_t need);
 // Largest log2 fan-in of one merge pass: the option, else the key type's default.
 int max_logf(const dsort_opts &opt, int type_default, int type_cap);
 

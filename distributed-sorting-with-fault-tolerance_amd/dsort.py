@@ -45,6 +45,7 @@ EXPORTS = [
     "dsort_parse_text_dev_i32", "dsort_parse_text_i32", "dsort_format_text_i32",
     "dsort_argsort_dev_i32", "dsort_sort_pairs_dev_i32", "dsort_gather_dev", "dsort_argsort_i32",
     "dsort_sample_argsort_dev_i32", "dsort_sample_sort_pairs_dev_i32",
+    "dsort_sample_gather_dev", "dsort_plan_gather_table", "dsort_plan_gather_route",
 ]
 
 
@@ -75,7 +76,8 @@ class Stats(ctypes.Structure):
                 ("sub_scatter_fallback", ctypes.c_int), ("exchange_path", ctypes.c_int),
                 ("first_level_map", ctypes.c_int),
                 ("fence_ranges", ctypes.c_int),  # ABI 6
-                ("deferred_frees", ctypes.c_int), ("pending_frees", ctypes.c_int)]
+                ("deferred_frees", ctypes.c_int), ("pending_frees", ctypes.c_int),
+                ("gather_sent", ctypes.c_size_t), ("gather_served", ctypes.c_size_t)]  # ABI 9
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -265,6 +267,9 @@ def load():
                                                         ctypes.POINTER(SZ), P]),
         "dsort_sample_sort_pairs_dev_i32": (ctypes.c_int, [P, P, P, SZ, ctypes.POINTER(P), ctypes.POINTER(P),
                                                            ctypes.POINTER(SZ), P]),
+        "dsort_sample_gather_dev": (ctypes.c_int, [P, P, SZ, U64, P, SZ, P, ctypes.c_int, P]),
+        "dsort_plan_gather_table": (ctypes.c_int, [ctypes.c_int, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
+        "dsort_plan_gather_route": (ctypes.c_int, [ctypes.c_int, P, P, P, ctypes.c_int, P, SZ, P, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -320,6 +325,38 @@ def plan_cuts(sorted_keys, my_rank, nranks, sv, sr, si):
     _check(None, f(_ptr(sorted_keys), sorted_keys.size, my_rank, nranks, _ptr(sv), _ptr(sr),
                    _ptr(si), _ptr(cuts)))
     return cuts
+
+
+def plan_gather_table(first, count):
+    """The distributed gather's owner table (dsort_plan_gather_table) from every rank's range
+    [first[r], first[r] + count[r]): (lo, hi, owner) of the non-empty ranges, sorted by lo."""
+    lib = load()
+    first = np.ascontiguousarray(first, np.uint64)
+    count = np.ascontiguousarray(count, np.uint64)
+    nranks = first.size
+    assert count.size == nranks
+    lo, hi = np.zeros(nranks, np.uint64), np.zeros(nranks, np.uint64)
+    owner = np.zeros(nranks, np.int32)
+    nr = ctypes.c_int()
+    _check(None, lib.dsort_plan_gather_table(nranks, _ptr(first), _ptr(count), _ptr(lo), _ptr(hi), _ptr(owner),
+                                             ctypes.byref(nr)))
+    return lo[:nr.value], hi[:nr.value], owner[:nr.value]
+
+
+def plan_gather_route(lo, hi, owner, nranks, idx):
+    """The gather's routing on the host (dsort_plan_gather_route): (counts, pos); counts has
+    nranks + 1 entries, the last counting the indices nobody owns, pos[j] is index j's place in the
+    owner-major, input-order-stable request layout."""
+    lib = load()
+    lo = np.ascontiguousarray(lo, np.uint64)
+    hi = np.ascontiguousarray(hi, np.uint64)
+    owner = np.ascontiguousarray(owner, np.int32)
+    idx = np.ascontiguousarray(idx, np.uint32)
+    counts = np.zeros(nranks + 1, np.uint64)
+    pos = np.zeros(max(idx.size, 1), np.uint64)
+    _check(None, lib.dsort_plan_gather_route(lo.size, _ptr(lo), _ptr(hi), _ptr(owner), nranks, _ptr(idx), idx.size,
+                                             _ptr(counts), _ptr(pos)))
+    return counts, pos[:idx.size]
 
 
 def write_text_i32(path, keys):
@@ -679,6 +716,42 @@ class Context:
                                                             ctypes.byref(vp), ctypes.byref(nout), self._stream()))
         k, v = self._slices((kp, vp), nout.value, keys.device)
         return k, v
+
+    # ---------------- distributed record gather (dsort.h, ABI 9) ----------------------------
+    def sample_gather_dev(self, records, first, idx, out=None):
+        """out[j] = the record at GLOBAL position idx[j], wherever it lives
+        (dsort_sample_gather_dev; collective).  `records` is this rank's contiguous CUDA tensor of
+        records -- a record is one row, of 4, 8 or 16 bytes, as for gather_dev -- holding the global
+        positions first .. first + len(records) - 1; idx is an int32 tensor of uint32 bit patterns,
+        e.g. the index slice of sample_argsort_dev.  Returns `out`, shaped
+        (len(idx),) + records.shape[1:]."""
+        n = self._i32(idx, "idx").numel()
+        if not records.is_contiguous() or records.dim() < 1:
+            raise DsortError("gather: a contiguous tensor of records is required")
+        rec = records.element_size()
+        for d in records.shape[1:]:
+            rec *= int(d)
+        if rec not in (4, 8, 16):
+            raise DsortError(f"gather: records of {rec} bytes (4, 8 or 16)")
+        shape = (n,) + tuple(records.shape[1:])
+        if out is None:
+            out = torch.empty(shape, dtype=records.dtype, device=records.device)
+        if out.dtype != records.dtype or tuple(out.shape) != shape or not out.is_contiguous():
+            raise DsortError("gather: out must hold len(idx) records of the records' type and row shape")
+        n_src = int(records.shape[0])
+        self.check(self.lib.dsort_sample_gather_dev(self.h, records.data_ptr() if n_src else None, n_src, int(first),
+                                                    idx.data_ptr() if n else None, n, out.data_ptr() if n else None,
+                                                    rec, self._stream()))
+        return out
+
+    def sample_sort_records_dev(self, keys, records, first):
+        """Distributed sort of records by an int32 key: sample_argsort_dev, then sample_gather_dev
+        with the returned indices.  keys[i] is the key of records[i], global position first + i.
+        Returns (sorted_keys, records_of_my_slice)."""
+        if int(records.shape[0]) != keys.numel():
+            raise DsortError("sample_sort_records_dev: one record per key is required")
+        k, i = self.sample_argsort_dev(keys, first)
+        return k, self.sample_gather_dev(records, first, i)
 
     def copy_d2h(self, host, dptr, nbytes):
         self.check(self.lib.dsort_copy_d2h(self.h, _ptr(host), dptr, nbytes))

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DSORT_ABI_VERSION 8
+#define DSORT_ABI_VERSION 9
 
 #define DSORT_OK 0
 #define DSORT_EINVAL (-1)   /* bad argument */
@@ -99,6 +99,10 @@ typedef struct dsort_stats {
     int deferred_frees;       /* the last sample sort: arenas it replaced while keys were in flight,
                                  whose release waited for the exchange's end */
     int pending_frees;        /* ... of those, still held when it returned (0, failed or not) */
+    /* ABI 9: set by the last dsort_sample_gather_dev, which touches no other field (a sort
+     * resets them to 0) */
+    size_t gather_sent;       /* requests this rank shipped to OTHER ranks                      */
+    size_t gather_served;     /* requests it served from its own records, its own included      */
 } dsort_stats;
 
 /* ---------------------------------------------------------------- lifecycle ---------- */
@@ -324,8 +328,8 @@ int dsort_sample_merge_dev_i64(dsort_ctx *ctx, const int64_t *d_sorted, size_t n
  *
  * Contract, as for dsort_sample_sort_dev_*: the inputs are not modified; on return *n_out is this
  * rank's slice length and *d_keys_out, *d_idx_out / *d_vals_out point to context-owned arrays of
- * *n_out elements, valid until the next sample sort or pair call on this context or
- * dsort_finalize.  The unpack is queued on `stream`: the arrays are ready after the stream.
+ * *n_out elements, valid until the next sample sort or pair call (a gather is neither) on this
+ * context or dsort_finalize.  The unpack is queued on `stream`: the arrays are ready after the stream.
  * d_keys_out == NULL: the sorted keys are not wanted.  Concatenating the slices of ranks
  * 0..nranks-1 gives the global order -- argsort: ascending by key, equal keys in ascending global
  * position (stable); pairs: ascending by key, equal keys by value as UNSIGNED 32-bit.  A rank with
@@ -340,9 +344,8 @@ int dsort_sample_merge_dev_i64(dsort_ctx *ctx, const int64_t *d_sorted, size_t n
  * Memory: the pair arena (8 * n_local bytes) and 8 * n_out bytes of output arrays (4 * n_out
  * without the keys), all grow-only, on top of the int64 sample sort's memory for these counts.
  *
- * Not offered: delivering wider payload records to the rank that holds their key (a distributed
- * gather needs an exchange of its own; on one rank dsort_gather_dev applies the indices as
- * before); int64 keys with a payload; the presorted / fault-survivor entry
+ * Wider payload records reach the rank that holds their key through dsort_sample_gather_dev (ABI 9,
+ * below).  Not offered: int64 keys with a payload; the presorted / fault-survivor entry
  * (dsort_sample_merge_dev_*) for pairs; the C master and workers, which move bare keys. */
 
 /* Global stable argsort.  The rank's chunk d_keys[0..n_local) holds the global positions
@@ -357,6 +360,56 @@ int dsort_sample_argsort_dev_i32(dsort_ctx *ctx, const int32_t *d_keys, size_t n
 int dsort_sample_sort_pairs_dev_i32(dsort_ctx *ctx, const int32_t *d_keys, const uint32_t *d_vals,
                                     size_t n_local, int32_t **d_keys_out, uint32_t **d_vals_out,
                                     size_t *n_out, void *stream);
+
+/* ABI 9: the distributed record gather -- payloads follow their keys across ranks.
+ *   d_dst[j] = the record at GLOBAL position d_idx[j], j < n_idx, wherever it lives.
+ * This rank owns the records at global positions first .. first + n_src - 1 (d_src[0..n_src)), and
+ * d_idx holds the n_idx global positions it wants, e.g. the index slice of
+ * dsort_sample_argsort_dev_i32: argsort, then one gather per payload column.
+ *
+ * Algorithm, a request/reply exchange over the communicator (either transport): 0. all-gather of
+ * every rank's (first, n_src, elem_bytes) -- the range table; 1. all-gather of every rank's request
+ * counts per owner, plus one column counting its indices nobody owns; 2. all-to-all-v of the
+ * requests (uint32 local indices, routed by a stable partition of d_idx by owner); the owners serve
+ * them with the kernel of dsort_gather_dev; 3. the reverse all-to-all-v of the records, which are
+ * then put back into the order of d_idx.  At one rank nothing is sent and every kernel still runs.
+ *
+ * Contract: collective -- every rank of the communicator calls it.  A rank with n_src == 0 and/or
+ * n_idx == 0 (its pointers may then be NULL) still joins every collective.  elem_bytes is 4, 8 or
+ * 16 as for dsort_gather_dev; records and indices need 4-byte alignment only.  The inputs are not
+ * modified; d_dst (caller-owned, n_idx records, no overlap with the inputs) is ready after
+ * `stream`.  d_idx may be the context-owned index array of dsort_sample_argsort_dev_i32: a gather
+ * uses arenas of its own and invalidates no slice of a sample sort, so several payload columns can
+ * be gathered from one argsort.  The ranks' ranges may come in any rank order; indices may repeat,
+ * may all name one owner and need not be a permutation.  n_idx < 2^32.
+ *
+ * Errors.  Checked before any memory or collective is touched, DSORT_EINVAL: a NULL ctx (plain
+ * return), elem_bytes not 4 / 8 / 16, first + n_src > 2^32, n_idx >= 2^32, a NULL pointer whose
+ * count is non-zero.  Without a communicator: DSORT_ECOMM, as dsort_sample_sort_dev_*.  More than
+ * 256 ranks (the owner table's fixed size): DSORT_EINVAL on every rank before the first collective.
+ * Checked symmetrically -- every rank returns DSORT_EINVAL from the same call, the communicator and
+ * the context stay usable: two non-empty ranges that overlap, ranks that disagree on elem_bytes
+ * (both seen by every rank in the range table) and an index that no rank owns (any non-zero entry
+ * of the count matrix's extra column; the message names the first such rank and its count; no
+ * request has moved by then).  This does not rely on the host transport's status gates.
+ * DSORT_OPT_COMM_TIMEOUT_MS, dsort_comm_abort, dsort_comm_deadline_ms, the host transport's status
+ * gates and DSORT_OPT_TEST_FAIL_EXCHANGE work as in a sample sort, k counting the gather's own four
+ * collectives as numbered above (0 = the range-table all-gather).  DSORT_OPT_KILL_AFTER_STAGE and
+ * DSORT_OPT_KILL_IN_EXCHANGE do not act on a gather.
+ *
+ * dsort_get_stats: the call sets gather_sent and gather_served and nothing else, so the preceding
+ * sample sort's statistics stay readable.
+ *
+ * Memory (context arenas of the gather's own, grow-only): with W = elem_bytes and m the requests
+ * this rank receives, 4 n_idx + 4 m + W m + W n_idx bytes, plus at most 2.1 MB of routing tables;
+ * on the host transport the pinned staging of the sample sort (max(4 n_idx, W m) and
+ * max(4 m, W n_idx) bytes).
+ *
+ * Not offered: records wider than 16 bytes in one call (gather the columns one by one).  The RCCL
+ * path has run with one rank only. */
+int dsort_sample_gather_dev(dsort_ctx *ctx, const void *d_src, size_t n_src, uint64_t first,
+                            const uint32_t *d_idx, size_t n_idx, void *d_dst, int elem_bytes,
+                            void *stream);
 
 /* ---------------------------------------------------------------- sample-sort planning  */
 /* Host-side planning rules of the sample sort, exported so that the CPU tests (gloo, no GPU)
@@ -380,6 +433,20 @@ int dsort_plan_cuts_i64(const int64_t *sorted, size_t n, int my_rank, int nranks
                         const uint64_t *split_idx, uint64_t *cuts);
 /* Regular sample positions of a local run of n keys: s indices (j+1)*n/(s+1), j<s. */
 int dsort_plan_sample_positions(size_t n, int s, uint64_t *idx);
+/* The distributed gather's host rules (ABI 9).
+ * dsort_plan_gather_table: from every rank's range [first[r], first[r] + count[r]) the owner table:
+ * the non-empty ranges sorted by their start, range i = [lo[i], hi[i]) owned by rank owner[i]
+ * (arrays of nranks entries, *nranges of them written).  DSORT_EINVAL when two ranges overlap or one
+ * ends beyond 2^32.
+ * dsort_plan_gather_route: the routing of n indices by that table, as the kernels do it (the same
+ * owner lookup: a binary search over lo, compared as unsigned, and a check against hi):
+ * counts[r] = the indices rank r owns, counts[nranks] = those nobody owns; pos[j] = the place of
+ * index j in the request layout -- owner-major, input order inside an owner (stable), the unowned
+ * ones last. */
+int dsort_plan_gather_table(int nranks, const uint64_t first[], const uint64_t count[], uint64_t lo[],
+                            uint64_t hi[], int32_t owner[], int *nranges);
+int dsort_plan_gather_route(int nranges, const uint64_t lo[], const uint64_t hi[], const int32_t owner[],
+                            int nranks, const uint32_t *idx, size_t n, uint64_t counts[], uint64_t pos[]);
 
 /* ---------------------------------------------------------------- utilities ---------- */
 /* Synthetic workload generators on the GPU: key i = f(splitmix64(seed+first+i)).

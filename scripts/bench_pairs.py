@@ -22,6 +22,15 @@ call of --steps back-to-back calls, its pack / sample sort / unpack legs from th
 and dsort_argsort_dev_i32 with its legs on the same keys in the same process; it reports the ratio
 and the excess leg by leg (bench_sample).
 
+    python scripts/bench_pairs.py --gather [--log2 28] [--steps 10] [--out profiles/pairs_gather_bench.json]
+
+--gather measures the distributed record gather (dsort_sample_gather_dev) on one RCCL rank: 2^28
+records of 16 bytes, indices a random permutation, --steps back-to-back calls against
+dsort_gather_dev on the same data in the same process, results compared bit for bit; its five legs
+(route | request exchange | serve | reply exchange | unroute) from the library's HIP events
+(dsort_sample_gather_leg_ms), and each streaming leg as a fraction of a device-to-device copy of
+the same byte total in the same run (bench_gather).
+
 Writes the JSON file and prints one summary line.  No GPU: fails (there is nothing to measure).
 """
 import argparse
@@ -172,6 +181,79 @@ def bench_sample(torch, dsort, ctx, n, steps, warmup):
     }
 
 
+def bench_gather(torch, dsort, ctx, n, steps, warmup, W=16):
+    """--gather: dsort_sample_gather_dev on ONE RCCL rank against dsort_gather_dev on the same
+    records and indices.  One rank ships nothing, and there is no shortcut to the local gather:
+    every kernel runs, the two exchanges are the device-to-device copies of the rank's own part, so
+    the legs are what a rank pays around the links."""
+    ctx.comm_init(1, 0, dsort.Context.unique_id())
+    D = W // 4
+    rec = torch.empty(n * D, dtype=torch.int32, device="cuda")
+    ctx.gen_uniform(rec, 0xC0FFEE, 0)
+    rec = rec.view(n, D)
+    idx = torch.randperm(n, device="cuda").to(torch.int32)
+    torch.cuda.empty_cache()
+    out = torch.empty_like(rec)
+    ref = torch.empty_like(rec)
+    leg_fn = ctx.lib.dsort_sample_gather_leg_ms  # not in dsort.h: the bench's view of the legs' events
+    leg_fn.restype = ctypes.c_int
+    leg_fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+    names = ("route", "request_exchange", "serve", "reply_exchange", "unroute")
+
+    def dist():
+        ctx.sample_gather_dev(rec, 0, idx, out=out)
+
+    def local():
+        ctx.gather_dev(rec, idx, ref)
+
+    local_ms = timed(torch, local, steps, warmup)
+    dist_ms = timed(torch, dist, steps, warmup)
+    legs = []
+    for _ in range(steps):
+        dist()
+        ms = (ctypes.c_double * 5)()
+        ctx.check(leg_fn(ctx.h, ms))
+        legs.append(tuple(ms))
+    leg_ms = [statistics.median(x[i] for x in legs) for i in range(5)]
+    st = ctx.stats()
+    torch.cuda.synchronize()
+    exact = bool(torch.equal(out, ref))
+    ctx.comm_destroy()
+    del out, ref
+    torch.cuda.empty_cache()
+    # HBM bytes of the streaming legs: route = count (4n) + place (4n + 4n); the exchanges are the
+    # copies of the own part (read + write); unroute reads idx and the replies and writes the records
+    leg_bytes = {"route": 12 * n, "request_exchange": 8 * n, "reply_exchange": 2 * W * n, "unroute": (4 + 2 * W) * n}
+    r4 = lambda x: round(x, 4)  # noqa: E731
+    gbs = lambda b, ms: b / (ms * 1e-3) / 1e9  # noqa: E731
+    streaming = {}
+    for leg, total in leg_bytes.items():
+        src = torch.empty(total // 2, dtype=torch.uint8, device="cuda")
+        dst = torch.empty_like(src)
+        src.zero_()
+        copy_ms = timed(torch, lambda: dst.copy_(src), steps, warmup)
+        del src, dst
+        torch.cuda.empty_cache()
+        ms = leg_ms[names.index(leg)]
+        streaming[leg] = {"bytes": total, "gb_per_s": r4(gbs(total, ms)), "memcpy_ms": r4(copy_ms),
+                          "memcpy_gb_per_s": r4(gbs(total, copy_ms)), "frac_of_memcpy": r4(copy_ms / ms)}
+    top = max(range(5), key=lambda i: leg_ms[i])
+    return {
+        "n": n, "elem_bytes": W,
+        "sample_gather_ms": r4(dist_ms),
+        "local_gather_ms": r4(local_ms),
+        "sample_over_local": r4(dist_ms / local_ms),
+        "legs_ms": {k: r4(v) for k, v in zip(names, leg_ms)},
+        "legs_sum_ms": r4(sum(leg_ms)),
+        "dominant_leg": names[top],
+        "serve_over_local_gather": r4(leg_ms[2] / local_ms),
+        "bytes_per_record": {"sample_gather": 28 + 6 * W, "local_gather": 4 + 2 * W},
+        "streaming": streaming,
+        "gather_sent": st["gather_sent"], "gather_served": st["gather_served"],
+        "exact_vs_local_gather": exact,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2", type=int, nargs="+", default=None)
@@ -180,10 +262,14 @@ def main():
     ap.add_argument("--sample", action="store_true",
                     help="time dsort_sample_argsort_dev_i32 on one RCCL rank against the local argsort "
                          "(default 2^28 keys, profiles/pairs_sample_bench.json)")
+    ap.add_argument("--gather", action="store_true",
+                    help="time dsort_sample_gather_dev on one RCCL rank against dsort_gather_dev "
+                         "(default 2^28 records of 16 bytes, profiles/pairs_gather_bench.json)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.log2 = args.log2 or ([28] if args.sample else [28, 30])
-    args.out = args.out or os.path.join(REPO, "profiles", "pairs_sample_bench.json" if args.sample else "pairs_bench.json")
+    args.log2 = args.log2 or ([28] if args.sample or args.gather else [28, 30])
+    name = "pairs_gather_bench.json" if args.gather else "pairs_sample_bench.json" if args.sample else "pairs_bench.json"
+    args.out = args.out or os.path.join(REPO, "profiles", name)
 
     import torch
 
@@ -192,6 +278,23 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_pairs: no GPU visible (nothing is measured without one)")
     ctx = dsort.Context(0)
+    if args.gather:
+        res = {"what": "distributed record gather of 16-byte records on one RCCL rank (dsort_sample_gather_dev), "
+                       "indices a random permutation, against dsort_gather_dev of the same resident data, same "
+                       "process; ms per call of --steps back-to-back calls, legs from the HIP events between them "
+                       "(median)",
+               "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup,
+               "sizes": [bench_gather(torch, dsort, ctx, 1 << lg, args.steps, args.warmup) for lg in args.log2]}
+        ctx.close()
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"pairs_gather_bench": [{k: s[k] for k in ("n", "sample_gather_ms", "local_gather_ms",
+                                                                    "sample_over_local", "legs_ms", "dominant_leg",
+                                                                    "exact_vs_local_gather")}
+                                                 for s in res["sizes"]]}), flush=True)
+        return
     if args.sample:
         res = {"what": "global stable argsort of uniform int32 keys on one RCCL rank (dsort_sample_argsort_dev_i32) "
                        "against dsort_argsort_dev_i32 of the same resident keys, same process; ms per call of "
