@@ -110,6 +110,13 @@ def test_sort_stages(dsort_mod):
     assert stages(16384, 4) == 2                   # two tiles: + one merge pass
     assert stages(1 << 20, 4) == 3                 # 128 tiles: tile sort + 2 merge passes (F <= 16)
     assert stages((1 << 25) - 1, 4) == 1 + 3       # 4096 tiles: 12 bits in 3 passes
+    # the tile is 8192 keys for both widths (dsort_wave.hip: TILE_OF<T> = WK * WG<T>::WAVES)
+    for w in (8, 4):
+        assert stages(8192, w) == 1
+        assert stages(8193, w) == 2
+        assert stages(16 * 8192, w) == 2           # 16 tiles: one pass of fan-in 16
+        assert stages(16 * 8192 + 1, w) == 3
+        assert stages(256 * 8192 + 1, w) == 4
     m = ctypes.c_int()
     assert lib.dsort_sort_stages(None, 100, 2, ctypes.byref(m)) == -1
 
@@ -122,3 +129,93 @@ def test_sort_stages(dsort_mod):
     assert ss_stages(1 << 32, 8) == 3 and ss_stages(3 << 22, 3, 2) == 3 and ss_stages(1 << 30, 1) == 3
     assert ss_stages(1 << 20, 4) == stages(1 << 18, 4)
     assert lib.dsort_sample_sort_stages(None, 100, 2, 2, 4, ctypes.byref(m)) == -1
+
+
+def test_gpu_merge_tables_and_generators(dsort_mod):
+    """The expectations of tests/test_gpu_merge.py, checked before they reach the GPU: its constants
+    hang together, every generated run is ascending and of the asked length, the duplicate-heavy
+    kinds hold the shares they claim, and its pass and level formulas agree with
+    dsort_sort_stages(NULL, ...) under the default options."""
+    import test_gpu_merge as gm
+
+    lib = dsort_mod.load()
+
+    def stages(n, w):
+        m = ctypes.c_int()
+        assert lib.dsort_sort_stages(None, n, w, ctypes.byref(m)) == 0
+        return m.value
+
+    assert gm.TILE == {4: 8192, 8: 8192} and gm.MT == {4: 16384, 8: 8192}
+    assert gm.SLACK == {4: 512, 8: 256} and gm.TNOM == {4: 15360, 8: 7680}
+    assert gm.MAXF == {4: 32, 8: 16} and gm.KPC == {4: 4, 8: 2} and gm.WK == 1024
+    for w in (4, 8):
+        # the pass formula, at the sweep's sizes, the view sizes and the pass boundaries
+        sizes = [(t - 1) * gm.TILE[w] + r for t in gm.SWEEP_TILES for r in gm.SWEEP_REM] + gm.VIEW_SIZES
+        sizes += [gm.TILE[w], gm.TILE[w] + 1, 16 * gm.TILE[w], 16 * gm.TILE[w] + 1, 256 * gm.TILE[w] + 1]
+        for n in sizes:
+            tiles = -(-n // gm.TILE[w])
+            assert stages(n, w) == 1 + gm.sort_passes(tiles, w), (n, w)
+            assert gm.sort_passes(tiles, w) == gm.sort_passes(tiles, w, 4)  # the default cap is 4
+        assert gm.sort_passes(33, w, 1) == 6 and gm.sort_passes(32, w, 1) == 5
+        assert gm.sort_passes(33, w, 5) == 2 and gm.sort_passes(32, w, 5) == (1 if w == 4 else 2)  # int64: 5 acts as 4
+        # the level formula: a sort of k tiles under the default cap merges 16 runs per pass
+        for k in sorted(set(gm.K_VALUES[4] + gm.K_VALUES[8] + [255, 4096, 4097])):
+            if k * gm.TILE[w] < (1 << 25):
+                assert stages(k * gm.TILE[w], w) == (1 + gm.merge_levels(k, 16) if k > 1 else 1), (k, w)
+    assert [gm.merge_levels(k, 32) for k in (1, 2, 32, 33, 1024, 1025)] == [0, 1, 1, 2, 2, 3]
+    assert [gm.merge_levels(k, 16) for k in (1, 2, 16, 17, 256, 257)] == [0, 1, 1, 2, 2, 3]
+
+    for w in (4, 8):
+        info = np.iinfo(gm.DTYPE[w])
+        assert len(gm.merge_cases(w)) == len(set(gm.merge_cases(w)))
+        for k in gm.K_VALUES[w]:
+            for family in gm.families_of(k):
+                variants = gm.run_lengths(family, k, w)
+                assert variants == gm.run_lengths(family, k, w)  # the same in every process
+                for lens in variants:
+                    assert len(lens) == k and min(lens) >= 0 and sum(lens) > 0
+                    assert max(lens) <= (5 * gm.TNOM[w] + 333 if k < gm.BIG_K else 200)  # small shapes only
+                if family == "empties" and k >= 3:
+                    assert len(variants) == 3 and all(0 in v for v in variants)
+                    assert sum(1 for x in variants[2] if x) == 1
+                if family == "one_long":
+                    assert [v.index(5 * gm.TNOM[w] + 333) for v in variants] == sorted({0, k // 2, k - 1})
+                if family == "chunk":
+                    assert set(variants[0]) <= {gm.KPC[w] - 1, gm.KPC[w], gm.KPC[w] + 1}
+        # the kinds, on a shape with short and long runs and an empty one
+        lens = [0, 1, 5000, 3, 2 * gm.MT[w] + 1, 700, 0, 4000]
+        n = sum(lens)
+        for kind in gm.KINDS[w]:
+            runs = gm.merge_runs(kind, lens, w)
+            assert [r.size for r in runs] == lens and all(r.dtype == gm.DTYPE[w] for r in runs)
+            assert all((r[1:] >= r[:-1]).all() for r in runs), kind
+            cat = np.concatenate(runs)
+            vals, counts = np.unique(cat, return_counts=True)
+            if kind == "all_equal":
+                assert vals.size == 1
+            elif kind == "two_values":
+                assert vals.size == 2 and counts.min() > n // 3
+            elif kind in ("stairs_up", "stairs_down"):
+                assert all(np.unique(r).size == 1 for r in runs if r.size) and vals.size == 6
+            elif kind == "dups":
+                assert vals.min() >= -50 and vals.max() < 50 and counts.min() > n // 200
+            elif kind == "zipf":
+                assert counts.max() > n // 5
+            elif kind == "limits":
+                assert vals[0] == info.min and vals[-1] == info.max
+                assert 0.3 < counts[0] / n < 0.37 and 0.3 < counts[-1] / n < 0.37
+            elif kind == "low_half":
+                assert ((cat >> 32) == -0x1234).all() and vals.size > 0.99 * n
+                assert 0.7 < ((cat >> 31) & 1).mean() < 0.8  # bit 31 forced on half, random on the rest
+            elif kind == "high_half":
+                assert ((cat & 0xFFFFFFFF) == 0x89ABCDEF).all() and vals.size > 0.99 * n
+            else:
+                assert kind == "uniform" and vals.size > 0.99 * n
+    for w in (4, 8):
+        for kind in gm.SWEEP_KINDS:
+            a = gm.sort_keys(kind, 20001, w)
+            assert a.dtype == gm.DTYPE[w] and a.size == 20001
+            if kind != "uniform":
+                assert a.min() == np.iinfo(a.dtype).min and a.max() == np.iinfo(a.dtype).max
+            if kind == "few":
+                assert np.unique(a).size == 5

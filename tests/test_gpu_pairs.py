@@ -7,13 +7,14 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-TILE64 = 4096
+TILE64 = 8192  # the int64 sort's tile (dsort_wave.hip: TILE_OF<T> = WK * WG<T>::WAVES = 1024 * 8)
 EINVAL, ESTAGE = -1, -7
 I32 = np.iinfo(np.int32)
 
 SIZES = [0, 1, 2, 3, 4, 5, 7, 8, 9, 255, 256, 257, 1023, 1024, 1025,   # vector groups and the scalar tail
+         4095, 4096, 4097,                                             # (edges of a stale TILE64 = 4096: kept)
          TILE64 - 1, TILE64, TILE64 + 1, 2 * TILE64 - 1, 2 * TILE64, 2 * TILE64 + 1,  # int64 tile edges
-         9 * TILE64 + 77, 300001]                                      # several tiles and merge passes
+         9 * 4096 + 77, 9 * TILE64 + 77, 300001]                       # several tiles and merge passes
 KINDS = ["uniform", "equal", "few", "extremes", "sorted", "reverse"]
 
 
@@ -75,10 +76,12 @@ def test_argsort_vs_numpy(gpu_ctx, n, kind):
         assert np.array_equal(_host(idx), np.arange(n, dtype=np.int32))
     st = gpu_ctx.stats()
     assert st["keys_in"] == n and st["keys_out"] == n  # the inner int64 sort's statistics
+    if n == TILE64 + 1:  # a stale tile constant fails here instead of silently testing mid-tile sizes
+        assert st["tile_keys"] == TILE64 and st["merge_passes"] == 1, st
 
 
 @pytest.mark.parametrize("off", [1, 3])
-@pytest.mark.parametrize("n", [1025, 2 * TILE64 + 1])
+@pytest.mark.parametrize("n", [1025, 2 * 4096 + 1, 2 * TILE64 + 1])
 def test_argsort_misaligned_views(gpu_ctx, n, off):
     """Inputs and outputs start at element 1 / 3 of a larger tensor (pointers 4 / 12 mod 16); the
     elements around the output views keep their sentinel."""
@@ -106,42 +109,43 @@ def test_pairs_misaligned_views(gpu_ctx, off):
     """The same for the key-value sort, keys and values at different phases."""
     import torch
     SENT = 0x5A5A5A5A
-    n, pad = 2 * TILE64 + 1, 8
-    rng = np.random.default_rng(50 + off)
-    k = rng.integers(-3, 3, n, endpoint=True).astype(np.int32)
-    v = rng.integers(I32.min, I32.max, n, dtype=np.int32, endpoint=True)
-    voff = 4 - off  # 3 / 1: another phase than the keys
-    bufs = [torch.full((n + 2 * pad,), SENT, dtype=torch.int32, device="cuda") for _ in range(4)]
-    kin, vin, kout, vout = bufs
-    kin[off:off + n] = _dev(k)
-    vin[voff:voff + n] = _dev(v)
-    gpu_ctx.sort_pairs_dev(kin[off:off + n], vin[voff:voff + n], keys_out=kout[voff:voff + n],
-                           vals_out=vout[off:off + n])
-    order = np.lexsort((v.view(np.uint32), k))
-    assert np.array_equal(_host(kout[voff:voff + n]), k[order])
-    assert np.array_equal(_host(vout[off:off + n]), v[order])
-    for t, o in ((kin, off), (vin, voff), (kout, voff), (vout, off)):
-        h = _host(t)
-        assert (h[:o] == SENT).all() and (h[o + n:] == SENT).all()
+    for n in (2 * 4096 + 1, 2 * TILE64 + 1):
+        pad = 8
+        rng = np.random.default_rng(50 + off)
+        k = rng.integers(-3, 3, n, endpoint=True).astype(np.int32)
+        v = rng.integers(I32.min, I32.max, n, dtype=np.int32, endpoint=True)
+        voff = 4 - off  # 3 / 1: another phase than the keys
+        bufs = [torch.full((n + 2 * pad,), SENT, dtype=torch.int32, device="cuda") for _ in range(4)]
+        kin, vin, kout, vout = bufs
+        kin[off:off + n] = _dev(k)
+        vin[voff:voff + n] = _dev(v)
+        gpu_ctx.sort_pairs_dev(kin[off:off + n], vin[voff:voff + n], keys_out=kout[voff:voff + n],
+                               vals_out=vout[off:off + n])
+        order = np.lexsort((v.view(np.uint32), k))
+        assert np.array_equal(_host(kout[voff:voff + n]), k[order])
+        assert np.array_equal(_host(vout[off:off + n]), v[order])
+        for t, o in ((kin, off), (vin, voff), (kout, voff), (vout, off)):
+            h = _host(t)
+            assert (h[:o] == SENT).all() and (h[o + n:] == SENT).all()
 
 
 def test_argsort_keys_out_is_keys(gpu_ctx):
-    n = 9 * TILE64 + 77
-    a = _dist(np.random.default_rng(1), "few", n)
-    d = _dev(a)
-    ko, idx = gpu_ctx.argsort_dev(d, keys_out=d)
-    assert ko is d
-    _check_argsort(a, _host(d), _host(idx))
+    for n in (9 * 4096 + 77, 9 * TILE64 + 77):
+        a = _dist(np.random.default_rng(1), "few", n)
+        d = _dev(a)
+        ko, idx = gpu_ctx.argsort_dev(d, keys_out=d)
+        assert ko is d
+        _check_argsort(a, _host(d), _host(idx))
 
 
 def test_argsort_without_keys_out(gpu_ctx):
-    n = 9 * TILE64 + 77
-    a = _dist(np.random.default_rng(2), "extremes", n)
-    d = _dev(a)
-    ko, idx = gpu_ctx.argsort_dev(d)
-    assert ko is None
-    assert np.array_equal(_host(d), a)
-    _check_argsort(a, None, _host(idx))
+    for n in (9 * 4096 + 77, 9 * TILE64 + 77):
+        a = _dist(np.random.default_rng(2), "extremes", n)
+        d = _dev(a)
+        ko, idx = gpu_ctx.argsort_dev(d)
+        assert ko is None
+        assert np.array_equal(_host(d), a)
+        _check_argsort(a, None, _host(idx))
 
 
 def test_argsort_stage_never_reached_still_delivers(gpu_ctx, dsort_mod):
@@ -192,7 +196,7 @@ def test_null_pointers_are_einval(gpu_ctx):
 
 
 # ------------------------------------------------------------------------------ pairs
-@pytest.mark.parametrize("n", [5, TILE64 + 1, 300001])
+@pytest.mark.parametrize("n", [5, 4096 + 1, TILE64 + 1, 300001])
 def test_pairs_ties_order_by_unsigned_value(gpu_ctx, n):
     """Keys from [-3, 3], values over the whole uint32 range: a signed comparison of the values
     would put those >= 2^31 first."""

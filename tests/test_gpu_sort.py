@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 CASES = json.load(open(os.path.join(GOLDEN, "cases.json")))
 INT_MIN, INT_MAX = -(2**31), 2**31 - 1
 I64_MIN, I64_MAX = -(2**63), 2**63 - 1
-TILE32, TILE64 = 8192, 4096
+TILE32, TILE64 = 8192, 8192  # dsort_wave.hip: TILE_OF<T> = WK * WG<T>::WAVES = 1024 * 8, both widths
 WTILE = 8192  # int32 tile of the wave-register tile sort (dsort_wave.hip; merge tiles: 16384)
 
 
@@ -107,13 +107,32 @@ def test_sort_i32_vs_oracle(gpu_ctx, oracle, n, kind):
     assert np.array_equal(got, exp)
 
 
-@pytest.mark.parametrize("n", [0, 1, 5, TILE64 - 1, TILE64, TILE64 + 1, 9 * TILE64 + 77, 300001])
-@pytest.mark.parametrize("kind", ["uniform", "few", "extremes", "reverse"])
+# (4095 / 4096 / 4097 and 9 * 4096 + 77 were the "tile edges" of a stale TILE64 = 4096: kept as literals)
+@pytest.mark.parametrize("n", [0, 1, 2, 3, 5, 15, 16, 17, 1023, 1024, 1025, 4095, 4096, 4097,
+                               TILE64 - 1, TILE64, TILE64 + 1, 2 * TILE64 - 1, 2 * TILE64, 2 * TILE64 + 1,
+                               9 * 4096 + 77, 9 * TILE64 + 77, 300001])
+@pytest.mark.parametrize("kind", ["uniform", "few", "extremes", "reverse", "equal", "sorted"])
 def test_sort_i64_vs_oracle(gpu_ctx, oracle, n, kind):
     rng = np.random.default_rng(n * 13 + len(kind))
     a = _dist(rng, kind, n, np.int64)
     exp = oracle.merge_sort(a) if n <= 200000 else np.sort(a, kind="stable")
     assert np.array_equal(gpu_ctx.sort(a.copy()), exp)
+
+
+@pytest.mark.parametrize("dt,tile", [(np.int32, TILE32), (np.int64, TILE64)])
+def test_tile_constants_match_the_library(gpu_ctx, dt, tile):
+    """The tile sizes this file takes its edge sizes from are the library's: after a small sort and
+    after a merge, stats()["tile_keys"] is TILE32 / TILE64.  A stale constant fails here instead of
+    silently testing mid-tile sizes."""
+    rng = np.random.default_rng(tile)
+    a = _dist(rng, "uniform", tile + 1, dt)
+    assert np.array_equal(gpu_ctx.sort(a.copy()), np.sort(a, kind="stable"))
+    st = gpu_ctx.stats()
+    assert st["tile_keys"] == tile and st["merge_passes"] == 1, st
+    runs = [np.sort(_dist(rng, "uniform", m, dt)) for m in (tile + 1, 5, tile - 1)]
+    assert np.array_equal(gpu_ctx.merge(runs), np.sort(np.concatenate(runs), kind="stable"))
+    st = gpu_ctx.stats()
+    assert st["tile_keys"] == tile and st["merge_passes"] == 1, st
 
 
 @pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 8, 9, 16, 33])
@@ -268,6 +287,22 @@ def test_sort_i32_pass_boundaries(gpu_ctx, n):
     out = torch.empty_like(t)
     gpu_ctx.sort_dev(t, out)
     assert np.array_equal(out.cpu().numpy(), np.sort(host))
+
+
+@pytest.mark.parametrize("n,passes", [(16 * TILE64 + 1, 2), (256 * TILE64 + 1, 3)])
+def test_sort_i64_pass_boundaries(gpu_ctx, n, passes):
+    """The int64 twin: tile counts just past one and two merge passes of fan-in 16."""
+    import torch
+    t = torch.empty(n, dtype=torch.int64, device="cuda")
+    gpu_ctx.gen_uniform(t, 99, 0)
+    host = t.cpu().numpy()
+    out = torch.empty_like(t)
+    gpu_ctx.sort_dev(t, out)
+    torch.cuda.synchronize()
+    st = gpu_ctx.stats()
+    assert np.array_equal(out.cpu().numpy(), np.sort(host, kind="stable"))
+    assert np.array_equal(t.cpu().numpy(), host)  # input untouched
+    assert st["merge_passes"] == passes and st["tile_keys"] == TILE64, st
 
 
 def test_back_to_back_sorts_on_two_streams(gpu_ctx):
