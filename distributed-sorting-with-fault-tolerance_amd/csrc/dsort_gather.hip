@@ -31,17 +31,14 @@
 // (D2D) 4 + 4, serve 4 + W + W, replies' own part W + W, unroute 4 + W + W: 28 + 6 W in all, of
 // which the routing reads idx three times.
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 
 #include <stdint.h>
 
 #include <algorithm>
-#include <mutex>
 #include <string>
 #include <vector>
 
-#include "dsort_internal.h"
-#include "dsort_tx.h"
+#include "dsort_exch.h"
 
 namespace dsort {
 namespace ga {
@@ -302,65 +299,6 @@ static bool leg_event(dsort_ctx *ctx, int i, hipStream_t s) {
     return hipEventRecord(ctx->gat_ev[i], s) == hipSuccess;
 }
 
-// An RCCL call on the non-blocking communicator: ncclInProgress is success-so-far (dsort_api.hip).
-#define DSORT_NCCLNB(ctx, call)                                                           \
-    do {                                                                                  \
-        ncclResult_t r_ = (call);                                                         \
-        if (r_ != ncclSuccess && r_ != ncclInProgress) {                                  \
-            abort_comm_locked(ctx);                                                       \
-            return dsort::set_err((ctx), DSORT_ECOMM,                                     \
-                                  std::string(#call) + ": " + ncclGetErrorString(r_));    \
-        }                                                                                 \
-    } while (0)
-
-// All-to-all-v of `unit`-byte elements, the shape of the sample sort's key exchange (dsort_api.hip,
-// step 7): sbuf[soff[r] .. + scnt[r]) goes to rank r, which receives it at rbuf[roff[s] .. +
-// rcnt[s]) for source s (counts and offsets in elements).  RCCL: grouped send / receive on the
-// stream, the own part by a D2D copy.  Host transport: D2H, the caller's all-to-all-v, H2D through
-// the pinned staging buffers.
-static int exchange(dsort_ctx *ctx, TxSeq &txs, const char *sbuf, const std::vector<uint64_t> &scnt,
-                    const std::vector<uint64_t> &soff, uint64_t stotal, char *rbuf, const std::vector<uint64_t> &rcnt,
-                    const std::vector<uint64_t> &roff, uint64_t rtotal, size_t unit, hipStream_t s, double deadline,
-                    const char *what) {
-    const int P = ctx->nranks, me = ctx->rank;
-    int rc;
-    if (!ctx->has_transport) {
-        const size_t dw = unit / 4;  // (requests and records travel as dwords)
-        DSORT_NCCLNB(ctx, ncclGroupStart());
-        for (int r = 0; r < P; ++r) {
-            if (r == me) continue;
-            if (scnt[r]) DSORT_NCCLNB(ctx, ncclSend(sbuf + soff[r] * unit, scnt[r] * dw, ncclUint32, r, ctx->comm, s));
-            if (rcnt[r]) DSORT_NCCLNB(ctx, ncclRecv(rbuf + roff[r] * unit, rcnt[r] * dw, ncclUint32, r, ctx->comm, s));
-        }
-        DSORT_NCCLNB(ctx, ncclGroupEnd());
-        rc = exch_wait(ctx, s, false, deadline, (std::string(what) + " (enqueue)").c_str());
-        if (rc) return rc;
-        if (scnt[me])
-            DSORT_HIP(ctx, hipMemcpyAsync(rbuf + roff[me] * unit, sbuf + soff[me] * unit, scnt[me] * unit,
-                                          hipMemcpyDeviceToDevice, s));
-        return DSORT_OK;
-    }
-    rc = ensure_host(ctx, &ctx->xfer, &ctx->xfer_bytes, (stotal ? stotal : 1) * unit);
-    if (rc) return rc;
-    rc = ensure_host(ctx, &ctx->xfer2, &ctx->xfer2_bytes, (rtotal ? rtotal : 1) * unit);
-    if (rc) return rc;
-    if (stotal) DSORT_HIP(ctx, hipMemcpyAsync(ctx->xfer, sbuf, stotal * unit, hipMemcpyDeviceToHost, s));
-    rc = exch_wait(ctx, s, true, deadline, (std::string(what) + " (staging)").c_str());
-    if (rc) return rc;
-    std::vector<size_t> sc(P), sd(P), rcn(P), rd(P);
-    for (int r = 0; r < P; ++r) {
-        sc[r] = scnt[r] * unit;
-        sd[r] = soff[r] * unit;
-        rcn[r] = rcnt[r] * unit;
-        rd[r] = roff[r] * unit;
-    }
-    if ((rc = tx_fault_point(ctx))) return rc;
-    if ((rc = txs.alltoallv(ctx->xfer, sc.data(), sd.data(), ctx->xfer2, rcn.data(), rd.data(), what)))
-        return set_err(ctx, rc, txs.error());
-    if (rtotal) DSORT_HIP(ctx, hipMemcpyAsync(rbuf, ctx->xfer2, rtotal * unit, hipMemcpyHostToDevice, s));
-    return DSORT_OK;
-}
-
 static int plan_table(int nranks, const uint64_t *first, const uint64_t *count, uint64_t *lo, uint64_t *hi,
                       int32_t *owner, int *nranges) {
     std::vector<int> order;
@@ -381,35 +319,20 @@ static int plan_table(int nranks, const uint64_t *first, const uint64_t *count, 
 }
 
 // dsort_sample_gather_dev behind its argument checks.  One order bracket around the whole sequence:
-// the arenas are shared by calls that may run on other streams.  Holds the comm mutex like the
-// sample sort.
+// the arenas are shared by calls that may run on other streams.  One exchange call (dsort_exch.h),
+// like the sample sort.
 template <int W>
 static int sample_gather(dsort_ctx *ctx, const uint32_t *src, size_t n_src, uint64_t first, const uint32_t *idx,
                          size_t n_idx, uint32_t *dst, void *stream) {
-    std::unique_lock<std::mutex> lock(ctx->comm_mu);
-    if (ctx->abort_req.load()) {
-        abort_comm_locked(ctx);
-        return set_err(ctx, DSORT_ECOMM, "communicator aborted (dsort_comm_abort)");
-    }
-    if (!ctx->comm && !ctx->has_transport)
-        return set_err(ctx, DSORT_ECOMM, "communicator not initialised (dsort_comm_init)");
-    const int P = ctx->nranks, me = ctx->rank, NB = P + 1;
-    if (P > MAXR)
+    // the gather's four collectives: range table, counts, requests, replies
+    ExchCall call(ctx, stream, 4);
+    if (call.rc) return call.rc;
+    const int P = call.P, me = call.me, NB = P + 1;
+    const hipStream_t s = call.s;
+    const double deadline = call.deadline;
+    if (P > MAXR) {
+        call.finished();  // (every rank leaves here)
         return set_err(ctx, DSORT_EINVAL, "gather: more than 256 ranks (the owner table's fixed size)");
-    hipStream_t s = pick_stream(ctx, stream);
-    const double deadline = ctx->opt.comm_timeout_ms > 0 ? tx_now_ms() + (double)ctx->opt.comm_timeout_ms : 0.0;
-    const bool host_tx = ctx->has_transport;
-    // host transport: the gather's four collectives with their gates (dsort_tx.h); leaving before the
-    // last one on an error of this rank alone reports it to the peers at the next gate (the guard)
-    TxSeq txs(ctx->transport, P, deadline, 4);
-    struct TxScope {
-        dsort_ctx *c;
-        ~TxScope() { c->tx = nullptr; }
-    } tx_scope{ctx};
-    TxGuard tx_guard;
-    if (host_tx) {
-        ctx->tx = &txs;
-        tx_guard.seq = &txs;
     }
     ctx->gat_ev_ok = false;
     int rc = order_begin(ctx, s);
@@ -422,7 +345,7 @@ static int sample_gather(dsort_ctx *ctx, const uint32_t *src, size_t n_src, uint
     if (rc) return rc;
     for (int r = 0; r < P; ++r)
         if (all[3 * r + 2] != all[2]) {
-            tx_guard.finished = true;  // (every rank sees the same table and leaves here)
+            call.finished();  // (every rank sees the same table and leaves here)
             return set_err(ctx, DSORT_EINVAL, "gather: the ranks disagree on elem_bytes (rank 0 passes " +
                                                   std::to_string(all[2]) + ", rank " + std::to_string(r) + " " +
                                                   std::to_string(all[3 * r + 2]) + ")");
@@ -432,7 +355,7 @@ static int sample_gather(dsort_ctx *ctx, const uint32_t *src, size_t n_src, uint
     int nr = 0;
     for (int r = 0; r < P; ++r) f[r] = all[3 * r], c[r] = all[3 * r + 1];
     if (plan_table(P, f.data(), c.data(), lo.data(), hi.data(), own.data(), &nr)) {
-        tx_guard.finished = true;
+        call.finished();
         return set_err(ctx, DSORT_EINVAL, "gather: the ranks' record ranges overlap or end beyond 2^32");
     }
 
@@ -490,7 +413,7 @@ static int sample_gather(dsort_ctx *ctx, const uint32_t *src, size_t n_src, uint
     if (rc) return rc;
     for (int r = 0; r < P; ++r)
         if (mat[(size_t)r * NB + P]) {
-            tx_guard.finished = true;  // (every rank sees the same matrix and leaves here)
+            call.finished();  // (every rank sees the same matrix and leaves here)
             return set_err(ctx, DSORT_EINVAL, "gather: rank " + std::to_string(r) + " holds " +
                                                   std::to_string(mat[(size_t)r * NB + P]) +
                                                   " indices that no rank owns");
@@ -518,8 +441,9 @@ static int sample_gather(dsort_ctx *ctx, const uint32_t *src, size_t n_src, uint
     uint32_t *back = static_cast<uint32_t *>(ctx->gat_back);
 
     // 2. the requests
-    rc = exchange(ctx, txs, reinterpret_cast<const char *>(req), scnt, soff, n_idx, reinterpret_cast<char *>(rreq), rcnt,
-                  roff, m, 4, s, deadline, "gather request all-to-all");
+    // (requests and records travel as dwords)
+    rc = alltoallv(ctx, A2av{req, scnt.data(), soff.data(), n_idx, rreq, rcnt.data(), roff.data(), m, 4, ncclUint32}, s,
+                   deadline, "gather request all-to-all", "gather request all-to-all (staging)");
     if (rc) return rc;
     ev = leg_event(ctx, 2, s) && ev;
 
@@ -531,10 +455,10 @@ static int sample_gather(dsort_ctx *ctx, const uint32_t *src, size_t n_src, uint
     ev = leg_event(ctx, 3, s) && ev;
 
     // the replies: the reverse exchange
-    rc = exchange(ctx, txs, reinterpret_cast<const char *>(rep), rcnt, roff, m, reinterpret_cast<char *>(back), scnt,
-                  soff, n_idx, W, s, deadline, "gather reply all-to-all");
+    rc = alltoallv(ctx, A2av{rep, rcnt.data(), roff.data(), m, back, scnt.data(), soff.data(), n_idx, W, ncclUint32}, s,
+                   deadline, "gather reply all-to-all", "gather reply all-to-all (staging)");
     if (rc) return rc;
-    tx_guard.finished = true;
+    call.finished();
     ev = leg_event(ctx, 4, s) && ev;
 
     // 4. unroute: dst[j] = back[pos(j)]
@@ -543,7 +467,7 @@ static int sample_gather(dsort_ctx *ctx, const uint32_t *src, size_t n_src, uint
         DSORT_HIP(ctx, hipGetLastError());
     }
     ev = leg_event(ctx, 5, s) && ev;
-    if (!host_tx) {  // the receives must have landed before the caller reads dst
+    if (!call.host_tx) {  // the receives must have landed before the caller reads dst
         rc = exch_wait(ctx, s, true, deadline, "gather reply all-to-all");
         if (rc) return rc;
     }

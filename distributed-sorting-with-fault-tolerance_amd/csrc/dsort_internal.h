@@ -238,6 +238,9 @@ int set_err(dsort_ctx *ctx, int code, const std::string &msg);
 hipStream_t pick_stream(dsort_ctx *ctx, void *stream);
 int hip_err(dsort_ctx *ctx, hipError_t e, const char *what);
 int ensure(dsort_ctx *ctx, void **buf, size_t *have, size_t need, const char *what);
+// grow-only pinned host buffers: any, and the mirror of ctx->small
+int ensure_host(dsort_ctx *ctx, void **buf, size_t *have, size_t need);
+int ensure_small_host(dsort_ctx *ctx, size_t need);
 // hipFree / hipHostFree of a replaced buffer, deferred while ctx->poll_waits (see dsort_ctx)
 void release_dev(dsort_ctx *ctx, void *p);
 void release_host(dsort_ctx *ctx, void *p);
@@ -270,8 +273,8 @@ int sort_stages(const dsort_opts &opt, uint64_t n, int key_bytes);
 // arena around them (the pair sort) brackets its whole sequence as well.
 int order_begin(dsort_ctx *ctx, hipStream_t s);
 int order_end(dsort_ctx *ctx, hipStream_t s);
-// dsort_sample_sort_dev_i64 for the pair sample sort (dsort_pairs.hip; the sample sort is static in
-// dsort_api.hip).  Takes the comm mutex itself: the caller must not hold it.
+// dsort_sample_sort_dev_i64 for the pair sample sort (dsort_pairs.hip; the sample sort and the rest
+// of the exchange layer: dsort_exch.h).  Takes the comm mutex itself: the caller must not hold it.
 int sample_sort_packed(dsort_ctx *ctx, const int64_t *d_in, size_t n_local, int64_t **d_out, size_t *n_out,
                        void *stream);
 // Host waits of the sort: blocking, or (ctx->poll_waits) polling with the abort flag and deadline
@@ -287,18 +290,6 @@ struct PollPause {
     double t0 = -1.0;
     void operator()();
 };
-// Pieces of the sample sort's exchange (dsort_api.hip) that the distributed gather
-// (dsort_gather.hip) drives its own collectives with.  abort_comm_locked: the caller holds
-// ctx->comm_mu.  exch_wait: every wait of an exchange (stream, RCCL's asynchronous error, abort flag,
-// deadline).  tx_fault_point: DSORT_OPT_TEST_FAIL_EXCHANGE.  allgather_u64: `count` uint64 per rank
-// over either transport (the host transport's through ctx->tx, fault point included).
-void abort_comm_locked(dsort_ctx *ctx);
-int exch_wait(dsort_ctx *ctx, hipStream_t s, bool with_stream, double deadline, const char *what,
-              bool hold = false);
-int tx_fault_point(dsort_ctx *ctx);
-int allgather_u64(dsort_ctx *ctx, const uint64_t *src, size_t count, uint64_t *out, hipStream_t s,
-                  double deadline, const char *what);
-int ensure_host(dsort_ctx *ctx, void **buf, size_t *have, size_t need);
 // Largest log2 fan-in of one merge pass: the option, else the key type's default.
 int max_logf(const dsort_opts &opt, int type_default, int type_cap);
 

@@ -48,6 +48,7 @@
 
 #include "dsort_bucket.h"
 #include "dsort_internal.h"
+#include "dsort_tx.h"
 
 #include <rocprofiler-sdk-roctx/roctx.h>
 #include "dsort_part.h"
@@ -3131,13 +3132,8 @@ extern "C" int dsort_debug_sbstamps(void *host, size_t bytes) {
 // from different runs are emitted lower run first, like the reference's `<=` (client.c:152) and
 // lowest-index-wins argmin (server.c:504) -- unobservable for keys-only data.
 // ------------------------------------------------------------------------------------------
-static double mono_ms() {
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-}
 void PollPause::operator()() {
-    const double t = mono_ms();
+    const double t = tx_now_ms();
     if (t0 < 0) t0 = t;
     if (t - t0 < POLL_SPIN_MS) sched_yield();
     else usleep(20);
@@ -3152,7 +3148,7 @@ static int poll_done(dsort_ctx *ctx, hipError_t (*query)(void *), void *h, const
         if (q != hipErrorNotReady) return hip_err(ctx, q, what);
         if (comm && ctx->abort_req.load())
             return set_err(ctx, DSORT_ECOMM, std::string(what) + ": aborted by dsort_comm_abort (keys in flight)");
-        if (comm && ctx->poll_deadline > 0 && mono_ms() > ctx->poll_deadline)
+        if (comm && ctx->poll_deadline > 0 && tx_now_ms() > ctx->poll_deadline)
             return set_err(ctx, DSORT_ETIMEOUT, std::string(what) + ": no progress before the deadline (keys in flight)");
         pause();
     }

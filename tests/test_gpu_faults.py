@@ -80,7 +80,7 @@ def _sorted_slice_ok(ctx, ptr, nout, fp_in):
 def test_rccl_abort_and_rebuild_one_rank(gpu_ctx):
     """dsort_comm_init (non-blocking RCCL) -> sample sort -> dsort_comm_abort from a second thread
     while a sample sort runs -> the communicator is gone (DSORT_ECOMM) -> dsort_comm_init with a new
-    unique id -> sample sort again (dsort_api.hip: abort_comm_locked, exch_wait, dsort_comm_init)."""
+    unique id -> sample sort again (dsort_exchange.hip: abort_comm_locked, exch_wait; dsort_api.hip: dsort_comm_init)."""
     import torch
 
     import dsort
@@ -198,7 +198,7 @@ def test_held_exchange_times_out_at_the_deadline(gpu_ctx):
 def test_faulted_exchanges_release_replaced_arenas(gpu_ctx):
     """the arenas the second level replaces while the keys are in flight (their release
     deferred: a device-wide synchronize could hang on a dead peer's stream) are freed once no kernel
-    can touch them -- also when the exchange fails (dsort_api.hip sample_sort_bx: the abort, the
+    can touch them -- also when the exchange fails (dsort_exchange.hip sample_sort_bx: the abort, the
     sort stream's drain, then flush_later).  Three bucket exchanges of growing size, each ending in
     DSORT_ETIMEOUT at the held final wait for the all-to-all, after the second level has grown its
     arenas (a failure inside the waves takes the same release, round 5): every one

@@ -354,7 +354,7 @@ def test_stage_timing_off_sorts_the_same_and_records_nothing(gpu_ctx):
 
 
 def test_c3_receive_merge_8_runs_bit_exact(gpu_ctx):
-    """Config C3's per-rank receive merge (dsort_api.hip sample_sort step 8: the gather + merge of
+    """Config C3's per-rank receive merge (dsort_exchange.hip sample_sort step 8: the gather + merge of
     server.c:414-415 / 500-515): 8 sorted runs of 2^26 int32 keys inside one rank's key range
     (1/8 of the int32 range, as uniform input gives every rank) merged by dsort_merge_dev_i32,
     compared element for element with torch.sort."""
