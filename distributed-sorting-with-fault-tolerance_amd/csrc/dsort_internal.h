@@ -70,6 +70,7 @@ struct dsort_opts {
     int64_t sub_keys = -1;          // DSORT_OPT_SUB_KEYS: -1 = 3/16 of a tile, 0 = no second level
     int64_t sub_os = -1;            // DSORT_OPT_SUB_OVERSAMPLE: -1 = 8 (4 at sub-buckets <= TILE/8)
     int64_t sub_gather = 1;         // DSORT_OPT_SUB_GATHER
+    int64_t argsort_wide = 0;       // DSORT_OPT_ARGSORT_WIDE
 };
 
 // The context.  One per host thread, bound to one device.
@@ -108,6 +109,19 @@ struct dsort_ctx {
     size_t spairs_k_bytes = 0;
     void *spairs_v = nullptr;     // ... and their indices / values
     size_t spairs_v_bytes = 0;
+    // the int64 argsort and record sort (dsort_pairs64.hip); its first arena is `pairs`
+    void *a64_b = nullptr;        // the wide path's second arena of packed words: 8 B each
+    size_t a64_b_bytes = 0;
+    void *a64_idx = nullptr;      // the record sort's permutation: 4 B each
+    size_t a64_idx_bytes = 0;
+    void *a64_part = nullptr;     // the min/max reduction's per-workgroup partials and its result
+    size_t a64_part_bytes = 0;
+    hipEvent_t a64_mm_ev = nullptr;  // the min/max read-back into small_host
+    static constexpr int kA64Ev = 7;
+    hipEvent_t a64_ev[kA64Ev] = {};  // around its legs (created on first use)
+    int a64_legs = 0;             // ... those the last call recorded
+    bool a64_ev_ok = false;       // ... all of them
+    bool a64_minmax = false;      // the last call ran the reduction (the automatic mode)
     // the distributed gather (dsort_gather.hip): arenas of its own, so that a gather leaves the
     // slices of the preceding sample sort / argsort (recv2, spairs_k, spairs_v) alone
     void *gat_req = nullptr;      // this rank's requests, owner-major (4 B per index)

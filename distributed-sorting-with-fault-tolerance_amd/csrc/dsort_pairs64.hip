@@ -1,0 +1,482 @@
+// dsort_pairs64.hip -- stable argsort and record sort of int64 keys (dsort.h, ABI 10).
+//
+// No 128-bit composite: a position needs only b = ceil(log2 n) bits of a 64-bit word, which leaves
+// room for the key in two cases (plan_argsort64, the rule dsort_plan_argsort_i64 exports).
+//
+//   narrow, one pass   max - min of the keys fits the other 64 - b bits: one int64 sort of
+//                      u = (key - min) << b | position, handed to the sort as (int64)(u ^ 1 << 63)
+//                      so that its signed order is the unsigned order of u.
+//   wide, two passes   any other keys: two stable passes, least significant half first.
+//                      1. A[i] = (lo32(key) ^ 0x80000000) : i, sorted -- the low halves as unsigned;
+//                      2. B[j] = hi32(d_keys[p]) : j with p = low word of A[j], sorted -- the high
+//                         halves as signed, ties in the order of pass 1;
+//                      3. r -> j = low word of B[r], (lo, p) = A[j]: idx_out[r] = p and
+//                         keys_out[r] = hi32 : lo.
+//
+// Both run sort_device<int64_t> untouched on words that are all distinct, as dsort_pairs.hip does.
+// The kernels here are the work around it: a min/max reduction (two launches, no atomics), the pack
+// and unpack of the narrow word, and the wide path's pack, regroup and final kernels, the last two
+// with one random 8-byte read per element and four of them in flight per lane.
+//
+// Access shapes as in dsort_pairs.hip: a wave takes 256 elements, lane l those at 2l, 2l + 1 and
+// 128 + 2l, 128 + 2l + 1, so every 16-byte load and store of 8-byte elements is contiguous over
+// the wave (1 KiB) and the indices go out as two 8-byte stores of 512 contiguous bytes.  Outputs
+// are non-temporal stores.  The caller's pointers are typed at their element alignment (keys 8,
+// indices 4 bytes: a tensor view at element 1); groups count from element 0, where the arenas are
+// 16-byte aligned, and the n % 256 last elements go one by one.
+//
+// HBM bytes per element: min/max reads 8; the narrow pack reads 8 and writes 8, the
+// unpack reads 8 and writes 4 + 8 (keys wanted); the wide pack reads 8 and writes 8, the regroup
+// reads 8 + a random 8 and writes 8, the final kernel reads 8 + a random 8 and writes 4 + 8.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include <string>
+
+#include "dsort_internal.h"
+
+namespace dsort {
+namespace p64 {
+
+constexpr int NT = 256;          // threads per workgroup
+constexpr unsigned MAXWG = 2048; // workgroups of a launch (256 CUs x 8), the rest by grid stride
+
+// 16 bytes of the caller's keys: two int64 at 8-byte alignment
+typedef uint64_t k2_a8 __attribute__((ext_vector_type(2), aligned(8)));
+// 8 bytes of the caller's indices: two dwords at dword alignment
+typedef uint32_t u2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+// 16 bytes of an arena
+typedef uint64_t l2 __attribute__((ext_vector_type(2)));
+
+constexpr uint64_t SIGN = 1ull << 63;
+constexpr uint32_t BIAS = 0x80000000u;
+
+__device__ __forceinline__ uint64_t word(uint32_t hi, uint32_t lo) { return ((uint64_t)hi << 32) | lo; }
+
+// ------------------------------------------------------------------ min / max ------------
+__device__ __forceinline__ void wave_minmax(int64_t &lo, int64_t &hi) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const int64_t a = __shfl_xor((long long)lo, d, 64), b = __shfl_xor((long long)hi, d, 64);
+        lo = a < lo ? a : lo;
+        hi = b > hi ? b : hi;
+    }
+}
+
+// the workgroup's (min, max) from every lane's, valid in thread 0
+__device__ __forceinline__ void block_minmax(int64_t &lo, int64_t &hi) {
+    __shared__ int64_t sh[2 * (NT / 64)];
+    wave_minmax(lo, hi);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        sh[2 * w] = lo;
+        sh[2 * w + 1] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 1; i < NT / 64; ++i) {
+            lo = sh[2 * i] < lo ? sh[2 * i] : lo;
+            hi = sh[2 * i + 1] > hi ? sh[2 * i + 1] : hi;
+        }
+    }
+}
+
+// part[2 g], part[2 g + 1] = min, max of the keys workgroup g saw (grid-stride, 16-byte loads, two
+// in flight per lane)
+__global__ void __launch_bounds__(NT) minmax_kernel(const int64_t *__restrict__ keys, uint64_t n,
+                                                    int64_t *__restrict__ part) {
+    int64_t lo = INT64_MAX, hi = INT64_MIN;
+    const uint64_t groups = n >> 1;
+    const uint64_t stride = (uint64_t)gridDim.x * NT;
+    const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
+    auto take = [&](uint64_t v) {
+        const int64_t k = (int64_t)v;
+        lo = k < lo ? k : lo;
+        hi = k > hi ? k : hi;
+    };
+    uint64_t g = t;
+    for (; g + stride < groups; g += 2 * stride) {
+        const k2_a8 a = *reinterpret_cast<const k2_a8 *>(keys + 2 * g);
+        const k2_a8 b = *reinterpret_cast<const k2_a8 *>(keys + 2 * (g + stride));
+        take(a.x), take(a.y), take(b.x), take(b.y);
+    }
+    if (g < groups) {
+        const k2_a8 a = *reinterpret_cast<const k2_a8 *>(keys + 2 * g);
+        take(a.x), take(a.y);
+    }
+    if (t == 0 && (n & 1)) take((uint64_t)keys[n - 1]);
+    block_minmax(lo, hi);
+    if (threadIdx.x == 0) {
+        part[2 * blockIdx.x] = lo;
+        part[2 * blockIdx.x + 1] = hi;
+    }
+}
+
+// out[0], out[1] = min, max over the m workgroups' partials (one workgroup)
+__global__ void __launch_bounds__(NT) minmax_final_kernel(const int64_t *__restrict__ part, uint32_t m,
+                                                          int64_t *__restrict__ out) {
+    int64_t lo = INT64_MAX, hi = INT64_MIN;
+    for (uint32_t g = threadIdx.x; g < m; g += NT) {
+        lo = part[2 * g] < lo ? part[2 * g] : lo;
+        hi = part[2 * g + 1] > hi ? part[2 * g + 1] : hi;
+    }
+    block_minmax(lo, hi);
+    if (threadIdx.x == 0) {
+        out[0] = lo;
+        out[1] = hi;
+    }
+}
+
+// ------------------------------------------------------------------ pack -----------------
+// WIDE: the first pass's word, the biased low half over the position.  Else the narrow word.
+template <bool WIDE>
+__device__ __forceinline__ uint64_t pack_word(uint64_t key, uint64_t i, uint64_t kmin, int b) {
+    if (WIDE) return word((uint32_t)key ^ BIAS, (uint32_t)i);
+    return (((key - kmin) << b) | i) ^ SIGN;
+}
+
+template <bool WIDE>
+__global__ void __launch_bounds__(NT) pack64_kernel(const int64_t *__restrict__ keys, uint64_t *__restrict__ packed,
+                                                    uint64_t n, uint64_t kmin, int b) {
+    const uint64_t chunks = n >> 8;
+    const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * NT) >> 6;
+    const uint32_t l = threadIdx.x & 63;
+    for (uint64_t c = t >> 6; c < chunks; c += nwaves) {
+        const uint64_t e0 = (c << 8) + 2 * l, e1 = e0 + 128;
+        const k2_a8 k0 = *reinterpret_cast<const k2_a8 *>(keys + e0);
+        const k2_a8 k1 = *reinterpret_cast<const k2_a8 *>(keys + e1);
+        __builtin_nontemporal_store(
+            l2{pack_word<WIDE>(k0.x, e0, kmin, b), pack_word<WIDE>(k0.y, e0 + 1, kmin, b)},
+            reinterpret_cast<l2 *>(packed + e0));
+        __builtin_nontemporal_store(
+            l2{pack_word<WIDE>(k1.x, e1, kmin, b), pack_word<WIDE>(k1.y, e1 + 1, kmin, b)},
+            reinterpret_cast<l2 *>(packed + e1));
+    }
+    const uint64_t i = (chunks << 8) + t;  // the n % 256 last elements, one each
+    if (i < n) packed[i] = pack_word<WIDE>((uint64_t)keys[i], i, kmin, b);
+}
+
+// ------------------------------------------------------------------ narrow unpack --------
+// idx_out[i] = the low b bits of u = packed[i] ^ SIGN, keys_out[i] (NULL: not wanted) = (u >> b) + min
+__global__ void __launch_bounds__(NT) unpack64_kernel(const uint64_t *__restrict__ packed, int64_t *__restrict__ keys_out,
+                                                      uint32_t *__restrict__ idx_out, uint64_t n, uint64_t kmin,
+                                                      int b) {
+    const uint64_t mask = (1ull << b) - 1;
+    const uint64_t chunks = n >> 8;
+    const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * NT) >> 6;
+    const uint32_t l = threadIdx.x & 63;
+    for (uint64_t c = t >> 6; c < chunks; c += nwaves) {
+        const uint64_t e0 = (c << 8) + 2 * l, e1 = e0 + 128;
+        l2 a = *reinterpret_cast<const l2 *>(packed + e0);
+        l2 d = *reinterpret_cast<const l2 *>(packed + e1);
+        a ^= SIGN;
+        d ^= SIGN;
+        __builtin_nontemporal_store(u2_a4{(uint32_t)(a.x & mask), (uint32_t)(a.y & mask)},
+                                    reinterpret_cast<u2_a4 *>(idx_out + e0));
+        __builtin_nontemporal_store(u2_a4{(uint32_t)(d.x & mask), (uint32_t)(d.y & mask)},
+                                    reinterpret_cast<u2_a4 *>(idx_out + e1));
+        if (keys_out) {
+            __builtin_nontemporal_store(k2_a8{(a.x >> b) + kmin, (a.y >> b) + kmin},
+                                        reinterpret_cast<k2_a8 *>(keys_out + e0));
+            __builtin_nontemporal_store(k2_a8{(d.x >> b) + kmin, (d.y >> b) + kmin},
+                                        reinterpret_cast<k2_a8 *>(keys_out + e1));
+        }
+    }
+    const uint64_t i = (chunks << 8) + t;
+    if (i < n) {
+        const uint64_t u = packed[i] ^ SIGN;
+        idx_out[i] = (uint32_t)(u & mask);
+        if (keys_out) keys_out[i] = (int64_t)((u >> b) + kmin);
+    }
+}
+
+// ------------------------------------------------------------------ wide: regroup --------
+// B[j] = hi32(keys[p]) : j, p = the low word of A[j] (A sorted by the low halves)
+__global__ void __launch_bounds__(NT) regroup64_kernel(const uint64_t *__restrict__ A, const int64_t *__restrict__ keys,
+                                                       uint64_t *__restrict__ B, uint64_t n) {
+    const uint64_t chunks = n >> 8;
+    const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * NT) >> 6;
+    const uint32_t l = threadIdx.x & 63;
+    for (uint64_t c = t >> 6; c < chunks; c += nwaves) {
+        const uint64_t e0 = (c << 8) + 2 * l, e1 = e0 + 128;
+        const l2 a = *reinterpret_cast<const l2 *>(A + e0);
+        const l2 d = *reinterpret_cast<const l2 *>(A + e1);
+        // four independent random reads in flight
+        const uint64_t k0 = (uint64_t)keys[(uint32_t)a.x], k1 = (uint64_t)keys[(uint32_t)a.y];
+        const uint64_t k2 = (uint64_t)keys[(uint32_t)d.x], k3 = (uint64_t)keys[(uint32_t)d.y];
+        __builtin_nontemporal_store(
+            l2{word((uint32_t)(k0 >> 32), (uint32_t)e0), word((uint32_t)(k1 >> 32), (uint32_t)e0 + 1)},
+            reinterpret_cast<l2 *>(B + e0));
+        __builtin_nontemporal_store(
+            l2{word((uint32_t)(k2 >> 32), (uint32_t)e1), word((uint32_t)(k3 >> 32), (uint32_t)e1 + 1)},
+            reinterpret_cast<l2 *>(B + e1));
+    }
+    const uint64_t i = (chunks << 8) + t;
+    if (i < n) B[i] = word((uint32_t)((uint64_t)keys[(uint32_t)A[i]] >> 32), (uint32_t)i);
+}
+
+// ------------------------------------------------------------------ wide: final ----------
+// r -> j = the low word of B[r] (B sorted by the high halves), A[j] = (lo ^ BIAS) : p:
+// idx_out[r] = p, keys_out[r] (NULL: not wanted) = hi32 : lo
+__global__ void __launch_bounds__(NT) final64_kernel(const uint64_t *__restrict__ B, const uint64_t *__restrict__ A,
+                                                     int64_t *__restrict__ keys_out, uint32_t *__restrict__ idx_out,
+                                                     uint64_t n) {
+    const uint64_t chunks = n >> 8;
+    const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * NT) >> 6;
+    const uint32_t l = threadIdx.x & 63;
+    auto key_of = [](uint64_t bw, uint64_t aw) { return word((uint32_t)(bw >> 32), (uint32_t)(aw >> 32) ^ BIAS); };
+    for (uint64_t c = t >> 6; c < chunks; c += nwaves) {
+        const uint64_t e0 = (c << 8) + 2 * l, e1 = e0 + 128;
+        const l2 x = *reinterpret_cast<const l2 *>(B + e0);
+        const l2 y = *reinterpret_cast<const l2 *>(B + e1);
+        const uint64_t a0 = A[(uint32_t)x.x], a1 = A[(uint32_t)x.y];
+        const uint64_t a2 = A[(uint32_t)y.x], a3 = A[(uint32_t)y.y];
+        __builtin_nontemporal_store(u2_a4{(uint32_t)a0, (uint32_t)a1}, reinterpret_cast<u2_a4 *>(idx_out + e0));
+        __builtin_nontemporal_store(u2_a4{(uint32_t)a2, (uint32_t)a3}, reinterpret_cast<u2_a4 *>(idx_out + e1));
+        if (keys_out) {
+            __builtin_nontemporal_store(k2_a8{key_of(x.x, a0), key_of(x.y, a1)},
+                                        reinterpret_cast<k2_a8 *>(keys_out + e0));
+            __builtin_nontemporal_store(k2_a8{key_of(y.x, a2), key_of(y.y, a3)},
+                                        reinterpret_cast<k2_a8 *>(keys_out + e1));
+        }
+    }
+    const uint64_t i = (chunks << 8) + t;
+    if (i < n) {
+        const uint64_t bw = B[i];
+        const uint64_t aw = A[(uint32_t)bw];
+        idx_out[i] = (uint32_t)aw;
+        if (keys_out) keys_out[i] = (int64_t)key_of(bw, aw);
+    }
+}
+
+// ------------------------------------------------------------------ host -----------------
+static unsigned grid_for(uint64_t lanes) {
+    const uint64_t g = (lanes + NT - 1) / NT;
+    return (unsigned)(g > MAXWG ? MAXWG : (g ? g : 1));
+}
+
+// The host rule (dsort_plan_argsort_i64): bits of a position, and the passes the keys' range needs.
+static int plan_argsort64(uint64_t n, int64_t kmin, int64_t kmax, int *idx_bits, int *passes) {
+    if (n > (1ull << 32) || kmin > kmax) return DSORT_EINVAL;
+    int b = 1;
+    if (n > 2) b = 64 - __builtin_clzll(n - 1);
+    const uint64_t R = (uint64_t)kmax - (uint64_t)kmin;
+    if (idx_bits) *idx_bits = b;
+    if (passes) *passes = n == 0 ? 0 : ((R >> (64 - b)) == 0 ? 1 : 2);
+    return DSORT_OK;
+}
+
+// The legs' events of the last int64 argsort, for dsort_argsort64_leg_ms below.
+static void leg_event(dsort_ctx *ctx, hipStream_t s) {
+    if (!ctx->a64_ev_ok || ctx->a64_legs >= dsort_ctx::kA64Ev) return;
+    hipEvent_t &e = ctx->a64_ev[ctx->a64_legs];
+    ctx->a64_ev_ok = (e || hipEventCreate(&e) == hipSuccess) && hipEventRecord(e, s) == hipSuccess;
+    if (ctx->a64_ev_ok) ++ctx->a64_legs;
+}
+
+// min and max of keys[0..n), n > 0, on the host: two launches, a 16-byte copy into the pinned
+// mirror and one host wait.
+static int minmax(dsort_ctx *ctx, const int64_t *keys, size_t n, hipStream_t s, int64_t *kmin, int64_t *kmax) {
+    int rc = ensure(ctx, &ctx->a64_part, &ctx->a64_part_bytes, (size_t)(MAXWG + 1) * 16, "argsort min/max partials");
+    if (rc) return rc;
+    if ((rc = ensure_small_host(ctx, 16))) return rc;
+    if (!ctx->a64_mm_ev && hipEventCreateWithFlags(&ctx->a64_mm_ev, hipEventDisableTiming) != hipSuccess)
+        return set_err(ctx, DSORT_EHIP, "hipEventCreate");
+    int64_t *part = static_cast<int64_t *>(ctx->a64_part);
+    const unsigned grid = grid_for(((uint64_t)n + 3) / 4);
+    hipLaunchKernelGGL(minmax_kernel, dim3(grid), dim3(NT), 0, s, keys, (uint64_t)n, part);
+    DSORT_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(minmax_final_kernel, dim3(1), dim3(NT), 0, s, part, (uint32_t)grid, part + 2 * MAXWG);
+    DSORT_HIP(ctx, hipGetLastError());
+    DSORT_HIP(ctx, hipMemcpyAsync(ctx->small_host, part + 2 * MAXWG, 16, hipMemcpyDeviceToHost, s));
+    DSORT_HIP(ctx, hipEventRecord(ctx->a64_mm_ev, s));
+    if ((rc = sync_event(ctx, ctx->a64_mm_ev, "argsort min/max read-back"))) return rc;
+    const int64_t *h = static_cast<const int64_t *>(ctx->small_host);
+    *kmin = h[0];
+    *kmax = h[1];
+    return DSORT_OK;
+}
+
+// One inner sort of the call.  DSORT_OPT_KILL_AFTER_STAGE counts the call's sorts one after the
+// other: `done` = the stages of the sorts before this one, which this one's continue.
+static int inner_sort(dsort_ctx *ctx, uint64_t *words, size_t n, hipStream_t s, int *done) {
+    const int64_t kill = ctx->opt.kill_after_pass;
+    if (kill >= 0) ctx->opt.kill_after_pass = kill - *done;  // (>= 0: the earlier sorts never reached it)
+    const int rc = sort_device<int64_t>(ctx, reinterpret_cast<int64_t *>(words), reinterpret_cast<int64_t *>(words), n,
+                                        s, true);
+    ctx->opt.kill_after_pass = kill;
+    *done += ctx->stages_done;
+    return rc;
+}
+
+// d_idx_out[j] = the position in keys of the j-th smallest key, equal keys in input order;
+// keys_out (NULL: not wanted; may be keys: the pack / the regroup has consumed the keys before the
+// last kernel writes).  Asynchronous on s but for the min/max read-back of the automatic mode.
+static int argsort64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uint32_t *idx_out, size_t n,
+                     hipStream_t s) {
+    if (n == 0) {
+        ctx->stats = fresh_stats();
+        ctx->ev_mask = 0;
+        ctx->kev_used = 0;
+        return DSORT_OK;
+    }
+    // one bracket around the whole sequence: the arenas are shared by calls on different streams
+    int rc = order_begin(ctx, s);
+    if (rc) return rc;
+    rc = ensure(ctx, &ctx->pairs, &ctx->pairs_bytes, n * 8, "pair arena");
+    if (rc) return rc;
+    uint64_t *A = static_cast<uint64_t *>(ctx->pairs);
+    ctx->a64_legs = 0;
+    ctx->a64_ev_ok = ctx->ev_ok && ctx->opt.stage_timing;
+    ctx->a64_minmax = false;
+    int b = 0, passes = 2;
+    int64_t kmin = 0, kmax = 0;
+    leg_event(ctx, s);
+    if (!ctx->opt.argsort_wide) {
+        if ((rc = minmax(ctx, keys, n, s, &kmin, &kmax))) return rc;
+        if ((rc = plan_argsort64(n, kmin, kmax, &b, &passes)))
+            return set_err(ctx, DSORT_EHIP, "argsort: the min/max reduction returned min > max");
+        ctx->a64_minmax = true;
+        leg_event(ctx, s);
+    }
+    const unsigned grid = grid_for(((uint64_t)n + 3) / 4);
+    int done = 0, src;
+    if (passes == 1) {
+        hipLaunchKernelGGL((pack64_kernel<false>), dim3(grid), dim3(NT), 0, s, keys, A, (uint64_t)n, (uint64_t)kmin, b);
+        DSORT_HIP(ctx, hipGetLastError());
+        leg_event(ctx, s);
+        // DSORT_ESTAGE (the kill stage was never reached) leaves a valid output: the rest still runs
+        src = inner_sort(ctx, A, n, s, &done);
+        if (src && src != DSORT_ESTAGE) return src;
+        leg_event(ctx, s);
+        hipLaunchKernelGGL(unpack64_kernel, dim3(grid), dim3(NT), 0, s, A, keys_out, idx_out, (uint64_t)n,
+                           (uint64_t)kmin, b);
+        DSORT_HIP(ctx, hipGetLastError());
+    } else {
+        rc = ensure(ctx, &ctx->a64_b, &ctx->a64_b_bytes, n * 8, "argsort second arena");
+        if (rc) return rc;
+        uint64_t *B = static_cast<uint64_t *>(ctx->a64_b);
+        hipLaunchKernelGGL((pack64_kernel<true>), dim3(grid), dim3(NT), 0, s, keys, A, (uint64_t)n, (uint64_t)0, 0);
+        DSORT_HIP(ctx, hipGetLastError());
+        leg_event(ctx, s);
+        src = inner_sort(ctx, A, n, s, &done);
+        if (src && src != DSORT_ESTAGE) return src;
+        leg_event(ctx, s);
+        hipLaunchKernelGGL(regroup64_kernel, dim3(grid), dim3(NT), 0, s, A, keys, B, (uint64_t)n);
+        DSORT_HIP(ctx, hipGetLastError());
+        leg_event(ctx, s);
+        src = inner_sort(ctx, B, n, s, &done);
+        if (src && src != DSORT_ESTAGE) return src;
+        leg_event(ctx, s);
+        hipLaunchKernelGGL(final64_kernel, dim3(grid), dim3(NT), 0, s, B, A, keys_out, idx_out, (uint64_t)n);
+        DSORT_HIP(ctx, hipGetLastError());
+    }
+    leg_event(ctx, s);
+    ctx->stats.argsort_passes = passes;
+    if ((rc = order_end(ctx, s))) return rc;
+    if (src == DSORT_ESTAGE)
+        return set_err(ctx, DSORT_ESTAGE,
+                       "DSORT_OPT_KILL_AFTER_STAGE = " + std::to_string(ctx->opt.kill_after_pass) + ": this argsort of " +
+                           std::to_string(n) + " int64 keys has " + std::to_string(done) + " stages in " +
+                           std::to_string(passes) + " sort(s) (kill points 0.." + std::to_string(done - 1) + ")");
+    return src;
+}
+
+static int check_args(dsort_ctx *ctx, const void *keys, const void *out, size_t n) {
+    if ((uint64_t)n > (1ull << 32))
+        return set_err(ctx, DSORT_EINVAL, "argsort: more than 2^32 keys (a position must fit 32 bits)");
+    if (n && (!keys || !out)) return set_err(ctx, DSORT_EINVAL, "null argument");
+    return DSORT_OK;
+}
+
+}  // namespace p64
+}  // namespace dsort
+
+using namespace dsort;
+
+extern "C" {
+
+int dsort_plan_argsort_i64(size_t n, int64_t key_min, int64_t key_max, int *idx_bits, int *passes) {
+    return p64::plan_argsort64(n, key_min, key_max, idx_bits, passes);
+}
+
+int dsort_argsort_dev_i64(dsort_ctx *ctx, const int64_t *d_keys, int64_t *d_keys_out, uint32_t *d_idx_out, size_t n,
+                          void *stream) {
+    if (!ctx) return DSORT_EINVAL;
+    if (int rc = p64::check_args(ctx, d_keys, d_idx_out, n)) return rc;
+    return p64::argsort64(ctx, d_keys, d_keys_out, d_idx_out, n, pick_stream(ctx, stream));
+}
+
+int dsort_sort_records_dev_i64(dsort_ctx *ctx, const int64_t *d_keys, int64_t *d_keys_out, const void *d_src,
+                               void *d_dst, size_t n, int elem_bytes, void *stream) {
+    if (!ctx) return DSORT_EINVAL;
+    if (elem_bytes != 4 && elem_bytes != 8 && elem_bytes != 16)
+        return set_err(ctx, DSORT_EINVAL, "record sort: elem_bytes must be 4, 8 or 16");
+    if (int rc = p64::check_args(ctx, d_keys, d_dst, n)) return rc;
+    if (n && !d_src) return set_err(ctx, DSORT_EINVAL, "null argument");
+    hipStream_t s = pick_stream(ctx, stream);
+    if (n == 0) return p64::argsort64(ctx, d_keys, d_keys_out, nullptr, 0, s);  // (resets the statistics)
+    int rc = order_begin(ctx, s);
+    if (rc) return rc;
+    rc = ensure(ctx, &ctx->a64_idx, &ctx->a64_idx_bytes, n * 4, "record sort indices");
+    if (rc) return rc;
+    uint32_t *idx = static_cast<uint32_t *>(ctx->a64_idx);
+    const int src = p64::argsort64(ctx, d_keys, d_keys_out, idx, n, s);
+    if (src && src != DSORT_ESTAGE) return src;
+    const std::string msg = ctx->err;
+    // (the stream as the caller gave it: dsort_gather_dev picks the same one)
+    if ((rc = dsort_gather_dev(ctx, d_src, idx, d_dst, n, elem_bytes, stream))) return rc;
+    // the gather reads the index arena behind the argsort's bracket: the call ends here
+    if ((rc = order_end(ctx, s))) return rc;
+    return src ? set_err(ctx, src, msg) : DSORT_OK;
+}
+
+int dsort_argsort_i64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uint32_t *idx, size_t n) {
+    if (!ctx) return DSORT_EINVAL;
+    if (int rc = p64::check_args(ctx, keys, idx, n)) return rc;
+    if (n == 0) return DSORT_OK;
+    int rc = ensure(ctx, &ctx->io, &ctx->io_bytes, n * 8, "staging");
+    if (rc) return rc;
+    rc = ensure(ctx, &ctx->io2, &ctx->io2_bytes, n * 4, "staging 2");
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    int64_t *dk = static_cast<int64_t *>(ctx->io);
+    uint32_t *di = static_cast<uint32_t *>(ctx->io2);
+    DSORT_HIP(ctx, hipMemcpyAsync(dk, keys, n * 8, hipMemcpyHostToDevice, s));
+    const int src = p64::argsort64(ctx, dk, keys_out ? dk : nullptr, di, n, s);
+    if (src && src != DSORT_ESTAGE) return src;
+    if (keys_out) DSORT_HIP(ctx, hipMemcpyAsync(keys_out, dk, n * 8, hipMemcpyDeviceToHost, s));
+    DSORT_HIP(ctx, hipMemcpyAsync(idx, di, n * 4, hipMemcpyDeviceToHost, s));
+    DSORT_HIP(ctx, hipStreamSynchronize(s));
+    return src;
+}
+
+// Not part of the ABI (like dsort_pairs_leg_ms): device time of the last int64 argsort's legs from
+// HIP events between them, for scripts/bench_pairs.py --i64.  ms[0] = the min/max reduction with its
+// read-back (0 when DSORT_OPT_ARGSORT_WIDE skipped it); one pass: ms[1..3] = pack, sort, unpack;
+// two passes: ms[1..5] = pack, sort 1, regroup, sort 2, final.  *legs = the entries written (4 or
+// 6; ms must hold 6).  Blocks until that call has finished; DSORT_EINVAL when it recorded none.
+int dsort_argsort64_leg_ms(dsort_ctx *ctx, double ms[6], int *legs) {
+    if (!ctx || !ms || !legs) return DSORT_EINVAL;
+    const int first = ctx->a64_minmax ? 0 : 1;  // without the reduction the events start at the pack
+    const int nl = ctx->a64_legs - 1 + first;
+    if (!ctx->a64_ev_ok || (nl != 4 && nl != 6))
+        return set_err(ctx, DSORT_EINVAL, "no timed int64 argsort on this context");
+    DSORT_HIP(ctx, hipEventSynchronize(ctx->a64_ev[ctx->a64_legs - 1]));
+    ms[0] = 0;
+    for (int i = first; i < nl; ++i) {
+        float f = 0;
+        DSORT_HIP(ctx, hipEventElapsedTime(&f, ctx->a64_ev[i - first], ctx->a64_ev[i - first + 1]));
+        ms[i] = f;
+    }
+    *legs = nl;
+    return DSORT_OK;
+}
+
+}  // extern "C"

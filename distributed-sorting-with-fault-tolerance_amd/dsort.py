@@ -46,6 +46,7 @@ EXPORTS = [
     "dsort_argsort_dev_i32", "dsort_sort_pairs_dev_i32", "dsort_gather_dev", "dsort_argsort_i32",
     "dsort_sample_argsort_dev_i32", "dsort_sample_sort_pairs_dev_i32",
     "dsort_sample_gather_dev", "dsort_plan_gather_table", "dsort_plan_gather_route",
+    "dsort_argsort_dev_i64", "dsort_argsort_i64", "dsort_sort_records_dev_i64", "dsort_plan_argsort_i64",
 ]
 
 
@@ -55,7 +56,7 @@ OPTIONS = {"buckets": 1, "bucket_keys": 2, "bucket_oversample": 3,
            "comm_timeout_ms": 8,
            "sub_keys": 9, "sub_oversample": 10, "sub_gather": 11, "test_hold_exchange": 12,
            "test_fail_exchange": 13, "stage_timing": 14, "test_tile_cap": 15,
-           "test_wave_fence": 16}
+           "test_wave_fence": 16, "argsort_wide": 17}
 
 
 class DsortError(RuntimeError):
@@ -77,6 +78,7 @@ class Stats(ctypes.Structure):
                 ("first_level_map", ctypes.c_int),
                 ("fence_ranges", ctypes.c_int),  # ABI 6
                 ("deferred_frees", ctypes.c_int), ("pending_frees", ctypes.c_int),
+                ("argsort_passes", ctypes.c_int),  # ABI 10, in what was padding
                 ("gather_sent", ctypes.c_size_t), ("gather_served", ctypes.c_size_t)]  # ABI 9
 
     def as_dict(self):
@@ -270,6 +272,11 @@ def load():
         "dsort_sample_gather_dev": (ctypes.c_int, [P, P, SZ, U64, P, SZ, P, ctypes.c_int, P]),
         "dsort_plan_gather_table": (ctypes.c_int, [ctypes.c_int, P, P, P, P, P, ctypes.POINTER(ctypes.c_int)]),
         "dsort_plan_gather_route": (ctypes.c_int, [ctypes.c_int, P, P, P, ctypes.c_int, P, SZ, P, P]),
+        "dsort_argsort_dev_i64": (ctypes.c_int, [P, P, P, P, SZ, P]),
+        "dsort_argsort_i64": (ctypes.c_int, [P, P, P, P, SZ]),
+        "dsort_sort_records_dev_i64": (ctypes.c_int, [P, P, P, P, P, SZ, ctypes.c_int, P]),
+        "dsort_plan_argsort_i64": (ctypes.c_int, [SZ, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int),
+                                                  ctypes.POINTER(ctypes.c_int)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -357,6 +364,14 @@ def plan_gather_route(lo, hi, owner, nranks, idx):
     _check(None, lib.dsort_plan_gather_route(lo.size, _ptr(lo), _ptr(hi), _ptr(owner), nranks, _ptr(idx), idx.size,
                                              _ptr(counts), _ptr(pos)))
     return counts, pos[:idx.size]
+
+
+def plan_argsort_i64(n, key_min, key_max):
+    """The int64 argsort's host rule (dsort_plan_argsort_i64): (idx_bits, passes) for n keys whose
+    smallest and largest are key_min and key_max."""
+    b, p = ctypes.c_int(), ctypes.c_int()
+    _check(None, load().dsort_plan_argsort_i64(n, key_min, key_max, ctypes.byref(b), ctypes.byref(p)))
+    return b.value, p.value
 
 
 def write_text_i32(path, keys):
@@ -494,29 +509,53 @@ class Context:
                                                                 out.data_ptr(), self._stream()))
         return out
 
-    # ---------------- argsort, key-value sort, gather (int32 keys; dsort.h, ABI 7) --------
+    # ---------------- argsort, key-value sort, gather (dsort.h, ABI 7; int64 keys: ABI 10) ----
     @staticmethod
-    def _i32(t, what, n=None):
-        if t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1:
-            raise DsortError(f"{what}: a contiguous 1-d int32 tensor is required")
+    def _i32(t, what, n=None, dtype=None):
+        dtype = torch.int32 if dtype is None else dtype
+        if t.dtype != dtype or not t.is_contiguous() or t.dim() != 1:
+            raise DsortError(f"{what}: a contiguous 1-d {str(dtype).split('.')[-1]} tensor is required")
         if n is not None and t.numel() != n:
             raise DsortError(f"{what}: {t.numel()} elements, expected {n}")
         return t
 
     def argsort_dev(self, keys, idx_out=None, keys_out=None):
-        """Stable argsort of an int32 CUDA tensor (dsort_argsort_dev_i32): returns
+        """Stable argsort of an int32 or int64 CUDA tensor (dsort_argsort_dev_i32 / _i64): returns
         (keys_out, idx).  idx[j] is the position in `keys` of the j-th smallest key, equal keys
         in input order.  idx is an int32 tensor holding the uint32 bit pattern (torch has no
         uint32 arithmetic): non-negative, and usable as an index, for n < 2^31.  keys_out=None:
         the sorted keys are not produced (None is returned for them); keys_out may be `keys`."""
-        n = self._i32(keys, "keys").numel()
+        kt = torch.int64 if keys.dtype == torch.int64 else torch.int32
+        n = self._i32(keys, "keys", dtype=kt).numel()
         if idx_out is None:
             idx_out = torch.empty(n, dtype=torch.int32, device=keys.device)
         self._i32(idx_out, "idx_out", n)
-        ko = None if keys_out is None else self._i32(keys_out, "keys_out", n).data_ptr()
-        self.check(self.lib.dsort_argsort_dev_i32(self.h, keys.data_ptr(), ko, idx_out.data_ptr(), n,
-                                                  self._stream()))
+        ko = None if keys_out is None else self._i32(keys_out, "keys_out", n, kt).data_ptr()
+        f = self.lib.dsort_argsort_dev_i64 if kt == torch.int64 else self.lib.dsort_argsort_dev_i32
+        self.check(f(self.h, keys.data_ptr(), ko, idx_out.data_ptr(), n, self._stream()))
         return keys_out, idx_out
+
+    def sort_records_dev(self, keys, records, keys_out=None, out=None):
+        """Stable sort of records by an int64 key (dsort_sort_records_dev_i64): records[i] belongs
+        to keys[i]; a record is one row of `records`, of 4, 8 or 16 bytes as for gather_dev; rows of
+        equal keys keep their input order.  keys_out (None: not wanted; may be `keys`) gets the
+        sorted keys.  Returns (keys_out, out), out holding the rows in key order."""
+        n = self._i32(keys, "keys", dtype=torch.int64).numel()
+        if not records.is_contiguous() or records.dim() < 1 or int(records.shape[0]) != n:
+            raise DsortError("sort_records_dev: one contiguous record per key is required")
+        rec = records.element_size()
+        for d in records.shape[1:]:
+            rec *= int(d)
+        if rec not in (4, 8, 16):
+            raise DsortError(f"sort_records_dev: records of {rec} bytes (4, 8 or 16)")
+        if out is None:
+            out = torch.empty_like(records)
+        if out.dtype != records.dtype or out.shape != records.shape or not out.is_contiguous():
+            raise DsortError("sort_records_dev: out must match the records' type and shape")
+        ko = None if keys_out is None else self._i32(keys_out, "keys_out", n, torch.int64).data_ptr()
+        self.check(self.lib.dsort_sort_records_dev_i64(self.h, keys.data_ptr(), ko, records.data_ptr(),
+                                                       out.data_ptr(), n, rec, self._stream()))
+        return keys_out, out
 
     def sort_pairs_dev(self, keys, vals, keys_out=None, vals_out=None):
         """Key-value sort of int32 CUDA tensors (dsort_sort_pairs_dev_i32): ascending by key, equal
@@ -549,12 +588,14 @@ class Context:
         return out
 
     def argsort(self, keys):
-        """Host form (dsort_argsort_i32): stable argsort of a numpy int32 array; returns
-        (sorted_keys, idx) as new arrays, idx of dtype uint32."""
-        keys = np.ascontiguousarray(keys, np.int32)
+        """Host form (dsort_argsort_i32 / _i64): stable argsort of a numpy array -- int64 as it is,
+        anything else as int32; returns (sorted_keys, idx) as new arrays, idx of dtype uint32."""
+        wide = isinstance(keys, np.ndarray) and keys.dtype == np.int64
+        keys = np.ascontiguousarray(keys, np.int64 if wide else np.int32)
         out = np.empty_like(keys)
         idx = np.empty(keys.size, np.uint32)
-        self.check(self.lib.dsort_argsort_i32(self.h, _ptr(keys), _ptr(out), _ptr(idx), keys.size))
+        f = self.lib.dsort_argsort_i64 if wide else self.lib.dsort_argsort_i32
+        self.check(f(self.h, _ptr(keys), _ptr(out), _ptr(idx), keys.size))
         return out, idx
 
     def gen_uniform(self, t, seed, first=0):

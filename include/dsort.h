@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DSORT_ABI_VERSION 9
+#define DSORT_ABI_VERSION 10
 
 #define DSORT_OK 0
 #define DSORT_EINVAL (-1)   /* bad argument */
@@ -99,6 +99,10 @@ typedef struct dsort_stats {
     int deferred_frees;       /* the last sample sort: arenas it replaced while keys were in flight,
                                  whose release waited for the exchange's end */
     int pending_frees;        /* ... of those, still held when it returned (0, failed or not) */
+    /* ABI 10 (in the four bytes that were padding here: no other field moves) */
+    int argsort_passes;       /* the last int64 argsort or record sort: 1 = the narrow word, one int64
+                                 sort; 2 = the wide path, two (0: it had no keys); 0 after every
+                                 other call (a sort resets it) */
     /* ABI 9: set by the last dsort_sample_gather_dev, which touches no other field (a sort
      * resets them to 0) */
     size_t gather_sent;       /* requests this rank shipped to OTHER ranks                      */
@@ -175,6 +179,11 @@ int dsort_synchronize(dsort_ctx *ctx);
                                          counts the ranges checked.  2 = the same, with one key of the
                                          first range flipped in between (the fence's own test: the
                                          sort must fail).  0 = off (default)                         */
+#define DSORT_OPT_ARGSORT_WIDE 17      /* ABI 10: the int64 argsort and record sort: 0 = one pass when the
+                                         keys' range allows it, else two (default; the call then reads
+                                         the keys' min and max first and waits for them on the host);
+                                         1 = always two passes (correct on any input, no host wait):
+                                         for tests and for the bench's A/B of the two paths          */
 int dsort_set_option(dsort_ctx *ctx, int option, int64_t value);
 int dsort_get_option(const dsort_ctx *ctx, int option, int64_t *value);
 
@@ -214,8 +223,8 @@ int dsort_sort_dev_copy_i64(dsort_ctx *ctx, const int64_t *d_in, int64_t *d_out,
  * its value are packed into one int64, (int64)key << 32 | (uint32)value, which the int64 sort
  * orders by key, then by value as unsigned.  Memory: an arena of 8 * n bytes in the context
  * (grow-only, like the others), on top of the int64 sort's own scratch for n keys.  int64 keys
- * with a payload are not offered: they would need a 128-bit composite.  All device pointers need
- * the alignment of their elements only (records of dsort_gather_dev: 4 bytes).
+ * with a payload: ABI 10, below.  All device pointers need the alignment of their elements only
+ * (records of dsort_gather_dev: 4 bytes).
  * DSORT_OPT_KILL_AFTER_STAGE acts as on an int64 sort of n keys: dsort_sort_stages(ctx, n, 8, ..)
  * gives the stage count, and with DSORT_ESTAGE the outputs are valid as for a sort.
  * dsort_get_stats afterwards shows that int64 sort's statistics (keys_in = keys_out = n). */
@@ -238,6 +247,53 @@ int dsort_gather_dev(dsort_ctx *ctx, const void *d_src, const uint32_t *d_idx, v
 /* Host form (synchronous, staged through the context's arenas like dsort_sort_i32): writes
  * idx (n entries) and, if non-NULL, keys_out (may equal keys).  n <= 2^32. */
 int dsort_argsort_i32(dsort_ctx *ctx, const int32_t *keys, int32_t *keys_out, uint32_t *idx, size_t n);
+
+/* ABI 10: the stable argsort and the record sort of int64 keys.  No 128-bit composite: a position
+ * needs only b = ceil(log2 n) bits of a 64-bit word (dsort_plan_argsort_i64), so
+ *   narrow, one pass:  when max - min of the keys fits the other 64 - b bits, one int64 sort of
+ *                      u = (uint64)(key - min) << b | position, handed to the sort as
+ *                      (int64)(u ^ 1 << 63) (signed order = unsigned order of u), is the stable
+ *                      argsort; unpack: position = u & (2^b - 1), key = (int64)((u >> b) + min);
+ *   wide, two passes:  any other keys take two stable passes, least significant half first: an
+ *                      int64 sort of (lo32(key) ^ 0x80000000) << 32 | position, then one of
+ *                      hi32(key) << 32 | j over the keys in that order, j their rank in it.
+ * Every packed word is distinct, as those of the int32 argsort.  n = 2^30 keys go narrow when they
+ * span less than 2^34, n = 2^20 less than 2^44.
+ *
+ * Memory (context arenas, grow-only, freed by dsort_finalize): narrow 8 n bytes (the pair arena of
+ * the int32 calls), wide 16 n bytes, the record sort 4 n bytes more for its permutation; on top of
+ * the int64 sort's own scratch for n keys and 32 KiB of reduction partials.
+ *
+ * Host wait: with DSORT_OPT_ARGSORT_WIDE = 0 (default) the call first reduces the keys' min and max
+ * on `stream` and WAITS for the 16 bytes on the host, once, as the bucketed sort waits for its own
+ * read-backs; everything else is queued on `stream`.  With DSORT_OPT_ARGSORT_WIDE = 1 nothing waits.
+ *
+ * DSORT_OPT_KILL_AFTER_STAGE acts inside the inner int64 sorts of n keys; the wide path's two sorts
+ * count one after the other, the second's stages continuing the first's numbering (2 x
+ * dsort_sort_stages(ctx, n, 8, ..) in all).  A stage never reached: DSORT_ESTAGE, every leg has
+ * run and the outputs are valid.  dsort_get_stats afterwards: argsort_passes, and the LAST inner
+ * sort's statistics (keys_in = keys_out = n). */
+
+/* The host rule: *idx_bits = b = 1 for n <= 2, else the bit length of n - 1 (2^32 keys: 32);
+ * with R = (uint64)key_max - (uint64)key_min, *passes = 1 if R >> (64 - b) is 0, else 2; n = 0: 0
+ * passes.  n > 2^32 or key_min > key_max: DSORT_EINVAL.  Either output may be NULL. */
+int dsort_plan_argsort_i64(size_t n, int64_t key_min, int64_t key_max, int *idx_bits, int *passes);
+/* Stable argsort, the contract of dsort_argsort_dev_i32: d_idx_out[j] = position in d_keys of the
+ * j-th smallest key, equal keys in input order; d_keys_out (NULL: not wanted; may equal d_keys)
+ * gets the sorted keys; d_keys is not modified unless aliased.  n <= 2^32 (else DSORT_EINVAL,
+ * before any memory is touched); n = 0 touches nothing.  Keys need 8-byte, indices 4-byte
+ * alignment only. */
+int dsort_argsort_dev_i64(dsort_ctx *ctx, const int64_t *d_keys, int64_t *d_keys_out,
+                          uint32_t *d_idx_out, size_t n, void *stream);
+/* Host form (synchronous, staged like dsort_argsort_i32). */
+int dsort_argsort_i64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uint32_t *idx, size_t n);
+/* Stable sort of records by an int64 key: d_dst[j] = d_src[idx[j]] for the argsort's idx (kept in
+ * a context arena), by dsort_gather_dev's kernel; record i of elem_bytes in {4, 8, 16} (else
+ * DSORT_EINVAL, checked first) belongs to d_keys[i].  Records of EQUAL keys keep their input order
+ * -- not the "by value as unsigned" rule of dsort_sort_pairs_dev_i32.  d_dst must not overlap
+ * d_src; d_keys_out may be NULL or equal d_keys.  n <= 2^32. */
+int dsort_sort_records_dev_i64(dsort_ctx *ctx, const int64_t *d_keys, int64_t *d_keys_out,
+                               const void *d_src, void *d_dst, size_t n, int elem_bytes, void *stream);
 
 /* ---------------------------------------------------------------- master merge ------- */
 /* Drop-in for the merge half of merge_chunks (server.c:481-515): merges k sorted host runs
@@ -345,8 +401,9 @@ int dsort_sample_merge_dev_i64(dsort_ctx *ctx, const int64_t *d_sorted, size_t n
  * without the keys), all grow-only, on top of the int64 sample sort's memory for these counts.
  *
  * Wider payload records reach the rank that holds their key through dsort_sample_gather_dev (ABI 9,
- * below).  Not offered: int64 keys with a payload; the presorted / fault-survivor entry
- * (dsort_sample_merge_dev_*) for pairs; the C master and workers, which move bare keys. */
+ * below).  Not offered across ranks: int64 keys with a payload (one GPU: ABI 10); the presorted /
+ * fault-survivor entry (dsort_sample_merge_dev_*) for pairs; the C master and workers, which move
+ * bare keys. */
 
 /* Global stable argsort.  The rank's chunk d_keys[0..n_local) holds the global positions
  * first .. first + n_local - 1 (`first` as in dsort_gen_uniform_*); (*d_idx_out)[j] is the global

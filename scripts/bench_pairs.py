@@ -31,6 +31,16 @@ dsort_gather_dev on the same data in the same process, results compared bit for 
 (dsort_sample_gather_leg_ms), and each streaming leg as a fraction of a device-to-device copy of
 the same byte total in the same run (bench_gather).
 
+    python scripts/bench_pairs.py --i64 [--log2 28 30] [--steps 10] [--out profiles/pairs_i64_bench.json]
+
+--i64 measures the stable argsort of int64 keys (dsort_argsort_dev_i64) on three inputs -- narrow
+(uniform in [-2^33, 2^33): one pass), wide (uniform over all 64 bits) and config C4's Zipf keys (both
+two passes): ms per call of --steps back-to-back calls, its legs from the library's HIP events
+(dsort_argsort64_leg_ms), torch.sort(stable=True) of the same keys in the same process (also the
+check, bit for bit), the narrow keys again with DSORT_OPT_ARGSORT_WIDE = 1, each streaming leg as a
+fraction of a device-to-device copy of the same byte total, and the two random-access legs against
+dsort_gather_dev of 8-byte records over a random permutation of the same n (bench_i64).
+
 Writes the JSON file and prints one summary line.  No GPU: fails (there is nothing to measure).
 """
 import argparse
@@ -254,6 +264,110 @@ def bench_gather(torch, dsort, ctx, n, steps, warmup, W=16):
     }
 
 
+# HBM bytes per element of the int64 argsort's legs with the sorted keys wanted (dsort_pairs64.hip);
+# "random" = of those, the bytes read at a random address
+I64_LEG_BYTES = {"minmax": 8, "pack": 16, "unpack": 20, "regroup": 24, "final": 28, "gather8": 20}
+I64_LEG_NAMES = {4: ("minmax", "pack", "sort", "unpack"), 6: ("minmax", "pack", "sort_lo", "regroup", "sort_hi", "final")}
+
+
+def bench_i64(torch, ctx, n, steps, warmup):
+    """--i64: dsort_argsort_dev_i64 on narrow, wide and Zipf keys against torch.sort(stable=True), the
+    narrow keys on both paths, and the legs against their yardsticks, all in this process."""
+    leg_fn = ctx.lib.dsort_argsort64_leg_ms  # not in dsort.h: the bench's view of the legs' events
+    leg_fn.restype = ctypes.c_int
+    leg_fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
+    r4 = lambda x: round(x, 4)  # noqa: E731
+    gbs = lambda b, ms: b / (ms * 1e-3) / 1e9  # noqa: E731
+    keys = torch.empty(n, dtype=torch.int64, device="cuda")
+    out = torch.empty_like(keys)
+    idx = torch.empty(n, dtype=torch.int32, device="cuda")
+
+    def call():
+        ctx.argsort_dev(keys, idx_out=idx, keys_out=out)
+
+    def measure():
+        ms = timed(torch, call, steps, warmup)
+        legs = []
+        for _ in range(steps):
+            call()
+            buf, cnt = (ctypes.c_double * 6)(), ctypes.c_int()
+            ctx.check(leg_fn(ctx.h, buf, ctypes.byref(cnt)))
+            legs.append(tuple(buf[:cnt.value]))
+        names = I64_LEG_NAMES[len(legs[0])]
+        st = ctx.stats()
+        return {"argsort_ms": r4(ms), "argsort_gkeys_per_s": r4(n / (ms * 1e-3) / 1e9),
+                "argsort_passes": st["argsort_passes"],
+                "legs_ms": {k: r4(statistics.median(x[i] for x in legs)) for i, k in enumerate(names)},
+                "last_inner_sort_stats": {k: st[k] for k in ("total_ms", "merge_passes", "tile_keys",
+                                                             "first_level_map")}}
+
+    # the yardsticks of this size: device-to-device copies of each streaming leg's byte total, and the
+    # local gather of 8-byte records over a random permutation
+    copies = {}
+    for leg in ("minmax", "pack", "unpack"):
+        total = I64_LEG_BYTES[leg] * n
+        src = torch.empty(total // 2, dtype=torch.uint8, device="cuda")
+        dst = torch.empty_like(src)
+        src.zero_()
+        copies[leg] = timed(torch, lambda: dst.copy_(src), steps, warmup)
+        del src, dst
+        torch.cuda.empty_cache()
+    perm = torch.randperm(n, device="cuda").to(torch.int32)
+    torch.cuda.empty_cache()
+    ctx.gen_uniform(keys, 0xC0FFEE, 0)
+    gather_ms = timed(torch, lambda: ctx.gather_dev(keys, perm, out), steps, warmup)
+    del perm
+    torch.cuda.empty_cache()
+
+    inputs = {}
+    for name in ("narrow", "wide", "zipf_c4"):
+        if name == "narrow":
+            ctx.gen_uniform(keys, 0x5EED2026, 0)
+            keys >>= 30  # arithmetic: uniform in [-2^33, 2^33)
+        elif name == "wide":
+            ctx.gen_uniform(keys, 0x5EED2026, 0)
+        else:
+            ctx.gen_zipf_i64(keys, 0x5EED2026, 0)
+        res = measure()
+        tvals, tidx = torch.sort(keys, stable=True)  # also the check
+        res["exact_vs_torch_sort_stable"] = bool(torch.equal(out, tvals) and torch.equal(idx.to(torch.int64), tidx))
+        del tvals, tidx
+        torch.cuda.empty_cache()
+        torch_ms = timed(torch, lambda: torch.sort(keys, stable=True), max(3, steps // 2), 1)
+        torch.cuda.empty_cache()
+        res["torch_sort_stable_ms"] = r4(torch_ms)
+        res["torch_over_argsort"] = r4(torch_ms / res["argsort_ms"])
+        if name == "narrow":  # the same keys through the two passes
+            ko1, io1 = out.clone(), idx.clone()
+            with ctx.options(argsort_wide=1):
+                forced = measure()
+            forced["exact_vs_automatic"] = bool(torch.equal(out, ko1) and torch.equal(idx, io1))
+            forced["wide_over_narrow"] = r4(forced["argsort_ms"] / res["argsort_ms"])
+            res["forced_wide"] = forced
+            del ko1, io1
+            torch.cuda.empty_cache()
+        legs = dict(res["legs_ms"])
+        if "forced_wide" in res:
+            legs.update({"wide_pack": res["forced_wide"]["legs_ms"]["pack"]})
+        res["streaming"] = {}
+        for leg, ms in legs.items():
+            ref = {"wide_pack": "pack"}.get(leg, leg)
+            if ref in copies and ms > 0:
+                total = I64_LEG_BYTES[ref] * n
+                res["streaming"][leg] = {"bytes": total, "gb_per_s": r4(gbs(total, ms)), "memcpy_ms": r4(copies[ref]),
+                                         "memcpy_gb_per_s": r4(gbs(total, copies[ref])),
+                                         "frac_of_memcpy": r4(copies[ref] / ms)}
+        ra = res.get("forced_wide", res)["legs_ms"]
+        if "regroup" in ra:
+            res["random_access"] = {
+                leg: {"bytes": I64_LEG_BYTES[leg] * n, "ms": ra[leg], "over_gather8": r4(ra[leg] / gather_ms),
+                      "bytes_over_gather8": r4(I64_LEG_BYTES[leg] / I64_LEG_BYTES["gather8"])}
+                for leg in ("regroup", "final")}
+        inputs[name] = res
+    return {"n": n, "gather8_random_perm_ms": r4(gather_ms), "gather8_bytes": I64_LEG_BYTES["gather8"] * n,
+            "leg_bytes_per_element": I64_LEG_BYTES, "inputs": inputs}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2", type=int, nargs="+", default=None)
@@ -265,10 +379,14 @@ def main():
     ap.add_argument("--gather", action="store_true",
                     help="time dsort_sample_gather_dev on one RCCL rank against dsort_gather_dev "
                          "(default 2^28 records of 16 bytes, profiles/pairs_gather_bench.json)")
+    ap.add_argument("--i64", action="store_true",
+                    help="time dsort_argsort_dev_i64 on narrow, wide and Zipf keys against torch.sort(stable=True) "
+                         "(default 2^28 and 2^30 keys, profiles/pairs_i64_bench.json)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     args.log2 = args.log2 or ([28] if args.sample or args.gather else [28, 30])
     name = "pairs_gather_bench.json" if args.gather else "pairs_sample_bench.json" if args.sample else "pairs_bench.json"
+    name = "pairs_i64_bench.json" if args.i64 else name
     args.out = args.out or os.path.join(REPO, "profiles", name)
 
     import torch
@@ -278,6 +396,25 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_pairs: no GPU visible (nothing is measured without one)")
     ctx = dsort.Context(0)
+    if args.i64:
+        res = {"what": "stable argsort of int64 keys, resident in HBM (dsort_argsort_dev_i64, sorted keys and indices): "
+                       "narrow = uniform in [-2^33, 2^33), wide = uniform over 64 bits, zipf_c4 = dsort_gen_zipf_i64; ms "
+                       "per call of --steps back-to-back calls, legs from the HIP events between them (median; minmax "
+                       "includes its 16-byte read-back and host wait), torch.sort(stable=True) of the same keys",
+               "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup,
+               "sizes": [bench_i64(torch, ctx, 1 << lg, args.steps, args.warmup) for lg in args.log2]}
+        ctx.close()
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"pairs_i64_bench": [{"n": s["n"], **{k: {"argsort_ms": v["argsort_ms"],
+                                                                 "passes": v["argsort_passes"],
+                                                                 "torch_over_argsort": v["torch_over_argsort"],
+                                                                 "exact": v["exact_vs_torch_sort_stable"]}
+                                                             for k, v in s["inputs"].items()}}
+                                              for s in res["sizes"]]}), flush=True)
+        return
     if args.gather:
         res = {"what": "distributed record gather of 16-byte records on one RCCL rank (dsort_sample_gather_dev), "
                        "indices a random permutation, against dsort_gather_dev of the same resident data, same "
