@@ -34,14 +34,11 @@ namespace bk {
 constexpr int BK_T = 1024;               // threads of the partition kernels
 constexpr int BK_MAXB = 1024;            // buckets at most (<= threads, one bucket per thread)
 constexpr int BK_OS = 32;                // samples per bucket
-#ifndef DSORT_BK_CHUNK
-#define DSORT_BK_CHUNK 16
-#endif
 // workgroups per column-sum chunk.  (Round 6: 64 -> 16 with the chunk prefixes scanned by
 // bucket_colscan_kernel: at 2^30 keys, 4681 histogram rows made 74 column-sum workgroups of 64
 // serial-ish loads per thread, and the one-workgroup scan walked 74 chunk rows per column --
 // column sums + scan + offsets took 68 us of a 7.6 ms sort.)
-constexpr int BK_CHUNK = DSORT_BK_CHUNK;
+constexpr int BK_CHUNK = 16;
 constexpr int BK_CSEG = 16;              // segments of the chunk rows per column (bucket_colscan_kernel)
 
 // Scatter sub-tile per key width: KPT keys per thread, SUB = BK_T * KPT keys staged in LDS
@@ -50,26 +47,21 @@ template <typename T> struct Geo;
 template <> struct Geo<int32_t> { static constexpr int KPT = 16; };  // (14: +0.09 ms; 12, 13 slower still)
 // int64: 48 KiB next to the 64 KiB carry (8 keys with the splitters read from global memory on
 // the lookups: C4 scatter 6.47 -> 7.09 ms)
-#ifndef DSORT_BK_KPT64
-#define DSORT_BK_KPT64 6
-#endif
-template <> struct Geo<int64_t> { static constexpr int KPT = DSORT_BK_KPT64; };
-// Bucket ids (int64, skewed keys): the histogram stores every key's bucket (2 bytes) and the
-// scatter reads it instead of repeating the lookup, when the lookup is the expensive one -- the log
-// slot map or one-key slots (BkMap.ids, set by bucket_slotmap_kernel): at 2^30 Zipf (C4) scatter
-// 6.52 -> 5.2-5.3 ms for histogram 2.08 -> 2.33 ms.  Uniform int64 keys (the linear map, no repeated
-// splitter) keep the lookup: there the scatter gained nothing and the histogram's writes cost
-// 1.50 -> 2.08 ms.  int32's packed lookup costs less than the 2 bytes per key would
-// (DSORT_BK_IDS32 builds it for comparison: histogram 0.77 -> 1.23 ms, scatter 2.67 -> 3.25 ms at
-// 2^30, profiles/r4_ab_bucket_ids_int32.log).
-// Round 6: three 10-bit buckets per word (DSORT_BK_IDS3, int64: KPT = 6 keys in two words, B <=
-// 1024) -- 1.33 bytes per key instead of 2: C4's id traffic 4.2 -> 2.8 GB, and the scatter still only
-// unpacks.  (One byte per key, the bucket above its slot's first, took it to 2.1 GB, but the scatter's
-// slot computation and table read cost more than the bytes saved: C4 11.84 -> 11.89 ms,
+constexpr int BK_KPT64 = 6;
+template <> struct Geo<int64_t> { static constexpr int KPT = BK_KPT64; };
+// Bucket ids (int64, skewed keys): the histogram stores every key's bucket and the scatter reads
+// it instead of repeating the lookup, when the lookup is the expensive one -- the log slot map or
+// one-key slots (BkMap.ids, set by bucket_slotmap_kernel): at 2^30 Zipf (C4), with 2 bytes per key,
+// scatter 6.52 -> 5.2-5.3 ms for histogram 2.08 -> 2.33 ms.  Uniform int64 keys (the linear map, no
+// repeated splitter) keep the lookup: there the scatter gained nothing and the histogram's writes
+// cost 1.50 -> 2.08 ms.  int32 has no ids: its packed lookup costs less than 2 bytes per key would
+// (measured: histogram 0.77 -> 1.23 ms, scatter 2.67 -> 3.25 ms at 2^30,
+// profiles/r4_ab_bucket_ids_int32.log).
+// Round 6: three 10-bit buckets per word (KPT = 6 keys in two words, B <= 1024) -- 1.33 bytes per
+// key instead of 2: C4's id traffic 4.2 -> 2.8 GB, and the scatter still only unpacks.  (One byte
+// per key, the bucket above its slot's first, took it to 2.1 GB, but the scatter's slot computation
+// and table read cost more than the bytes saved: C4 11.84 -> 11.89 ms,
 // profiles/r6_ab_ids8_dropped.log.)
-#ifndef DSORT_BK_IDS3
-#define DSORT_BK_IDS3 1
-#endif
 // Non-temporal stores (round 6) for the histogram's bucket ids and the int32 scatter's whole lines:
 // written once and read by a later kernel after gigabytes of other traffic, they gain nothing from
 // the caches.  2^30 int32 7.52 -> 7.46 ms of device time (4 of 4 interleaved runs), C4 10.81 ->
@@ -77,28 +69,17 @@ template <> struct Geo<int64_t> { static constexpr int KPT = DSORT_BK_KPT64; };
 // worse, and the fill of the pure buckets +0.25 ms (profiles/r6_ab_fill_nontemporal_dropped.log);
 // the sorted-runs instance (HT) keeps cached stores: its long streams of one bucket lost 0.05 ms
 // (sorted and reversed input, profiles/r6_ab_nt_other_inputs.log).
-#ifndef DSORT_IDS_NT
-#define DSORT_IDS_NT 1
-#endif
-#ifndef DSORT_LINES_NT
-#define DSORT_LINES_NT 1  // (bit 0: int32, bit 1: int64)
-#endif
 typedef int bk_v4i __attribute__((ext_vector_type(4)));
 typedef long long bk_v2l __attribute__((ext_vector_type(2)));
 template <typename T> struct BkIds {
-#ifdef DSORT_BK_IDS32
-    static constexpr bool ON = true;
-#else
     static constexpr bool ON = sizeof(T) == 8;
-#endif
-    static constexpr int PER_WORD = DSORT_BK_IDS3 && sizeof(T) == 8 ? 3 : 2;  // buckets per 32-bit word
-    static constexpr int BITS = PER_WORD == 3 ? 10 : 16;
+    static constexpr int PER_WORD = 3;  // buckets per 32-bit word
+    static constexpr int BITS = 10;
     static constexpr uint32_t MASK = (1u << BITS) - 1;
 };
 static_assert(BK_MAXB <= 1024, "10-bit bucket ids");
-// Ids of a sub-tile (SUB keys from key s): thread-major pairs (PER_WORD 2) -- thread t's KPT / 2 words
-// at s / 2 + KPT t / 2 --, or (PER_WORD 3) word w of thread t at (s / SUB) (KPT / 3) BK_T + w BK_T + t:
-// every access of a wave is 64 consecutive words.
+// Ids of a sub-tile (SUB keys from key s): word w of thread t at (s / SUB) (KPT / 3) BK_T + w BK_T
+// + t: every access of a wave is 64 consecutive words.
 
 struct TileRef {
     uint64_t base;   // first key of the tile
@@ -360,10 +341,10 @@ __device__ __forceinline__ void build_slots(const typename Comp<T>::C *spl, int 
 // Bucket of (key, index).  In a one-key slot the copies of K may go to any bucket from the
 // first of K's splitters to the one after the last (every one of those buckets holds keys <= K
 // before it and >= K after it, and the buckets strictly inside hold only K).  Since round 6
-// (bucket_onekey, DSORT_ONEKEY_HASH) they all go to the inner buckets, by a hash of the index.
+// (bucket_onekey) they all go to the inner buckets, by a hash of the index.
 // (Before: the two outer buckets took exactly the copies the composite order gives them (index <=
 // the first run splitter's, > the last one's) and the copies in between were split over the inner
-// buckets by index range, in proportion -- onekey_ab, kept for DSORT_ONEKEY_HASH=0.)
+// buckets by index range, in proportion.)
 // Histogram and scatter use the same map and table, so they agree key for key.  (Which copy of
 // K lands where does not matter to a keys-only sort.)
 // int32: the slot entry carries the slot's first splitter's key down to bit 1 (the slot is the
@@ -372,47 +353,26 @@ __device__ __forceinline__ void build_slots(const typename Comp<T>::C *spl, int 
 // to that splitter in bits 31..1 compares its composite; a slot of two or more splitters searches
 // them (their number is in the entry).  (Round 2 read the splitter for every key of a slot
 // that had one: half of the keys, a dependent 8-byte LDS read on the way to the rank atomic.)
-template <typename T>
-__device__ __forceinline__ int onekey_ab(const typename Comp<T>::C &a, const typename Comp<T>::C &z, int lo, int hi,
-                                         T key, const typename Comp<T>::C &c) {
-    const T K = Comp<T>::key_of(a);
-    const uint32_t i = Comp<T>::idx_of(c), ia = Comp<T>::idx_of(a), iz = Comp<T>::idx_of(z);
-    if (key != K || i <= ia) return key <= K ? lo : hi;
-    if (i > iz) return hi;
-    // hi - lo - 1 inner buckets over the indices (ia, iz] (the hardware reciprocal: the same
-    // instruction in the histogram and the scatter; IEEE division measured 0.25 ms slower)
-    const float q = (float)(i - ia - 1) * ((float)(hi - lo - 1) * __builtin_amdgcn_rcpf((float)(iz - ia)));
-    const int j = (int)q;
-    return lo + 1 + (j < hi - lo - 2 ? j : hi - lo - 2);
-}
 __device__ __forceinline__ int refine_inner(int lo, int hi, uint32_t idx);
-// Round 6 (DSORT_ONEKEY_HASH): the copies of K all go to the buckets strictly between K's first
+// Round 6 (bucket_onekey): the copies of K all go to the buckets strictly between K's first
 // and last splitter, spread by a hash of the index (as in the refined slot, refine_pick) -- one read
 // of K instead of two splitter reads (the int64 lookups are bound by LDS bandwidth, and C4 puts ~58 %
 // of its keys in one-key slots), no run of neighbouring copies piling onto one bucket's counter, and
 // the outer buckets hold only keys below / above K, so every copy of K lands in a pure bucket that
 // the second level skips.  2^30 keys: C4 (int64 Zipf) 11.7 -> 11.2 ms, 16 distinct int32 keys 7.9 ->
 // 5.2 ms, int32 keys of [1, 100] 6.1 -> 4.1 ms, uniform unchanged (profiles/r6_ab_onekey_hash_*.log).
-// (Bit 0: int64, bit 1: int32.)
-#ifndef DSORT_ONEKEY_HASH
-#define DSORT_ONEKEY_HASH 3
-#endif
 template <typename T>
 __device__ __forceinline__ int bucket_onekey(const typename Comp<T>::C *spl, int lo, int hi, T key,
                                              const typename Comp<T>::C &c) {
-    if constexpr ((DSORT_ONEKEY_HASH >> (sizeof(T) == 8 ? 0 : 1)) & 1) {
-        const T K = Comp<T>::key_of(spl[lo]);
-        if (key != K) return key < K ? lo : hi;
-        return refine_inner(lo, hi, Comp<T>::idx_of(c));
-    }
-    return onekey_ab<T>(spl[lo], spl[hi - 1], lo, hi, key, c);
+    const T K = Comp<T>::key_of(spl[lo]);
+    if (key != K) return key < K ? lo : hi;
+    return refine_inner(lo, hi, Comp<T>::idx_of(c));
 }
 // The refined slot (BkMap.r2s, int32 on the fixed map): the key's sub-slot entry, then
 //  - a one-key sub-slot (its splitters all hold K): a key other than K lies below or above all of
 //    them; the copies of K go to the buckets strictly between K's first and last splitter (each
-//    holds only K, so any of them keeps the order), spread by a hash of the index.  (The first
-//    level's one-key slots split K's copies by index range instead, which needs K's first and last
-//    splitter -- two more reads -- and piles a workgroup's copies onto one counter.)  When the
+//    holds only K, so any of them keeps the order), spread by a hash of the index, as in the first
+//    level's one-key slots (bucket_onekey).  When the
 //    sub-slot is one key value (key implied), no splitter is read at all;
 //  - else a search among the sub-slot's splitters (none to a few)
 // -- instead of a search over the whole slot's (e.g. ~500 splitters of 100 small keys, from global
@@ -604,7 +564,7 @@ __global__ void __launch_bounds__(BK_MAXB) bucket_slotmap_kernel(const typename 
             if (!refine) r2slot = ~0u;
             BkMap r = fixed ? am[0] : am[qa];
             r.ad = r.ulo != 0 || r.mode != 0 || r.sh != (uint32_t)(CT::KB - BK_SLOTB) ? 1u : 0u;
-            r.ids = BkIds<T>::ON ? 1u : 0u;  // (int32 with DSORT_BK_IDS32: always)
+            r.ids = 0;  // (int32 stores no bucket ids, BkIds)
             r.hot = bucket_runs_hint<T>(nasc, ndup, nsp);
             r.one = r.ad ? 1u : (ndup != 0);
             r.r2s = r.r2lo = r.r2sh = 0;
@@ -770,13 +730,10 @@ __global__ void __launch_bounds__(BK_MAXB) pair_splitter_kernel(const int64_t *_
 // branch of its own (an exec-mask save, a conditional jump), and the scatter's loads were not
 // issued together (int32 scatter 2.59 -> 2.49 ms, int64 Zipf 4.53 -> 4.45 ms).  The histogram keeps
 // the checks: unguarded, its int64 instance took 2.21 -> 3.09 ms at 2^30 Zipf (int32: no change).
-#ifndef DSORT_NOGUARD
-#define DSORT_NOGUARD 1
-#endif
 template <typename T, int KPT, bool UNGUARDED = true>
 __device__ __forceinline__ void load_sub(const T *__restrict__ in, uint64_t i0, uint64_t n, uint64_t sub_end,
                                          T (&x)[KPT]) {
-    if (UNGUARDED && DSORT_NOGUARD && sub_end <= n) {
+    if (UNGUARDED && sub_end <= n) {
 #pragma unroll
         for (int k = 0; k < KPT; ++k) x[k] = in[i0 + (uint64_t)k * BK_T];
     } else {
@@ -865,9 +822,10 @@ __global__ void __launch_bounds__(BK_T, 2) bucket_hist_kernel(const T *__restric
         if (sub + 1 < subs) load_sub<T, KPT, false>(in, b0 + SUB, n, b0 - threadIdx.x + 2 * SUB, nxt);
         // the buckets of the thread's keys, BkIds::PER_WORD per word (bucket ids)
         constexpr int PW = BkIds<T>::PER_WORD;
-        static_assert(!BkIds<T>::ON || KPT % PW == 0, "bucket ids: whole words per thread");
-        uint32_t idw[KPT / PW > 0 ? KPT / PW : 1] = {};
-        const auto idput = [&](int k, int b) { idw[k / PW] |= (uint32_t)b << (BkIds<T>::BITS * (k % PW)); };
+        uint32_t idw[BkIds<T>::ON ? KPT / PW : 1] = {};
+        const auto idput = [&](int k, int b) {
+            if constexpr (BkIds<T>::ON) idw[k / PW] |= (uint32_t)b << (BkIds<T>::BITS * (k % PW));
+        };
         // (the mode branch outside the key loop: a slot array would cost the second workgroup)
         if (m.hot) {  // (runs of one bucket: aggregated increments, bucket_runs_hint)
 #pragma unroll
@@ -901,24 +859,12 @@ __global__ void __launch_bounds__(BK_T, 2) bucket_hist_kernel(const T *__restric
                 }
             }
         }
-        // thread-major: the KPT ids of thread t of a sub-tile at words (sub-tile start + KPT t) / 2,
-        // i.e. a thread stores (and the scatter's thread loads) KPT / 2 consecutive words -- one
-        // 2-byte access per key measured slower than the lookup it replaces (int32)
-        if (BkIds<T>::ON && m.ids) {
-            if constexpr (PW == 3) {
-                uint32_t *dst = ids + (b0 - threadIdx.x) / SUB * (KPT / 3) * BK_T + threadIdx.x;
+        // word w of the sub-tile's ids: one wave stores 64 consecutive words (BkIds)
+        if constexpr (BkIds<T>::ON) {
+            if (m.ids) {
+                uint32_t *dst = ids + (b0 - threadIdx.x) / SUB * (KPT / PW) * BK_T + threadIdx.x;
 #pragma unroll
-                for (int w = 0; w < KPT / 3; ++w) {
-#if DSORT_IDS_NT
-                    __builtin_nontemporal_store(idw[w], dst + w * BK_T);
-#else
-                    dst[w * BK_T] = idw[w];
-#endif
-                }
-            } else {
-                uint32_t *dst = ids + (b0 - threadIdx.x) / 2 + (uint64_t)threadIdx.x * (KPT / 2);
-#pragma unroll
-                for (int w = 0; w < KPT / 2; ++w) dst[w] = idw[w];
+                for (int w = 0; w < KPT / PW; ++w) __builtin_nontemporal_store(idw[w], dst + w * BK_T);
             }
         }
     }
@@ -1138,8 +1084,8 @@ __device__ unsigned long long g_bkstamps[8192 * 16];
     do {        \
     } while (0)
 #endif
-// IDS: the variant that reads the histogram's buckets (BkIds).  The host launches both variants for
-// int64 (it does not know the map's choice); the one that does not match m.ids returns at once
+// IDS: the variant that reads the histogram's buckets (BkIds).  The host launches the one the map
+// chose (first_level reads BkMap.ids back); an instance that does not match m.ids returns at once
 // (one kernel with a run-time branch: uniform int64 scatter 5.29 -> 5.84 ms).
 // HT: the instance for input with runs of one bucket (BkMap.hot: sorted, reversed), which enters a
 // long line stream in the line map with the owner's whole wave.
@@ -1195,12 +1141,9 @@ __global__ void __launch_bounds__(BK_T) bucket_scatter_lines_kernel(const T *__r
     // -- and the host fills their output ranges with their key (bucket_sort: fill_segments_kernel),
     // write-only.  (Through the line streams they cost the scatter as much LDS work as any key: C4
     // has 47 % of its keys in pure buckets.)  pmask: bit b = bucket b is pure, one ballot per wave.
-#ifndef DSORT_DROP_PURE
-#define DSORT_DROP_PURE 1
-#endif
     __shared__ uint32_t pmask[BK_MAXB / 32];
     {
-        const uint64_t pb = __ballot(DSORT_DROP_PURE && pure != 0);
+        const uint64_t pb = __ballot(pure != 0);
         if (lane == 0 && 2 * w + 1 < BK_MAXB / 32) {
             pmask[2 * w] = (uint32_t)pb;
             pmask[2 * w + 1] = (uint32_t)(pb >> 32);
@@ -1210,9 +1153,7 @@ __global__ void __launch_bounds__(BK_T) bucket_scatter_lines_kernel(const T *__r
     // (the refined slot's table, BkMap.r2s: in the LDS the scatter has left)
     __shared__ uint32_t tab2s[ADP || IDS ? 1 : BK_R2];
     const uint32_t *tab2 = ADP || IDS ? nullptr : tab2s;
-#ifndef DSORT_IDS_ONLY
     if (BkIds<T>::ON && (m.ids != 0) != IDS) return;  // (workgroup-uniform: the other variant's sort)
-#endif
     if (!IDS) {
         load_splitters<T>(spl_g, BP, spl);
         if (!ADP && m.r2s)
@@ -1234,13 +1175,10 @@ __global__ void __launch_bounds__(BK_T) bucket_scatter_lines_kernel(const T *__r
     uint32_t nid[IDS ? KPT / PW : 1];  // (the histogram's bucket ids, PW per word)
     // the ids of the sub-tile from key s
     const auto load_ids = [&](uint64_t s) {
-        if constexpr (IDS && PW == 3) {
-            const uint32_t *src = ids + s / SUB * (KPT / 3) * BK_T + tb;
+        if constexpr (IDS) {
+            const uint32_t *src = ids + s / SUB * (KPT / PW) * BK_T + tb;
 #pragma unroll
-            for (int w = 0; w < KPT / 3; ++w) nid[w] = src[w * BK_T];
-        } else if constexpr (IDS) {
-#pragma unroll
-            for (int w = 0; w < KPT / 2; ++w) nid[w] = ids[s / 2 + (uint64_t)tb * (KPT / 2) + w];
+            for (int w = 0; w < KPT / PW; ++w) nid[w] = src[w * BK_T];
         }
     };
     load_sub<T, KPT>(in, g0 + tb, n, g0 + SUB, nxt);
@@ -1268,14 +1206,7 @@ __global__ void __launch_bounds__(BK_T) bucket_scatter_lines_kernel(const T *__r
             if constexpr (IDS) load_ids(s0 + SUB);
         }
         BKST(6);  // (the sub-tile's keys in, their slots)
-#ifndef DSORT_HOT_SCATTER
-#define DSORT_HOT_SCATTER 1
-#endif
-#ifndef DSORT_SCATTER_CB
-#define DSORT_SCATTER_CB 4  // keys per batch of the whole-sub-tile classify (int32, fixed map)
-#endif
-
-        if (DSORT_HOT_SCATTER && m.hot) {  // (runs of one bucket: aggregated ranks, bucket_runs_hint)
+        if (m.hot) {  // (runs of one bucket: aggregated ranks, bucket_runs_hint)
 #pragma unroll
             for (int k = 0; k < KPT; ++k) {
                 const uint64_t i = s0 + tb + (uint64_t)k * BK_T;
@@ -1287,7 +1218,7 @@ __global__ void __launch_bounds__(BK_T) bucket_scatter_lines_kernel(const T *__r
             }
         } else {
           bool batched = false;
-          if constexpr (!ADP && !IDS && DSORT_SCATTER_CB > 0) {
+          if constexpr (!ADP && !IDS) {
            if (s0 + SUB <= n) {
             batched = true;
             // (int32 on the fixed map, a whole sub-tile: no per-key bounds.)  The table reads of CB
@@ -1296,7 +1227,7 @@ __global__ void __launch_bounds__(BK_T) bucket_scatter_lines_kernel(const T *__r
             // before the next key's, with the key's bounds check as a branch around it).  The rare
             // slow keys of a batch (crowded slot, equal to the slot's splitter) take one
             // wave-uniform branch.
-            constexpr int CB = DSORT_SCATTER_CB > 0 ? DSORT_SCATTER_CB : 1;
+            constexpr int CB = 4;  // keys per batch
 #pragma unroll
             for (int k0 = 0; k0 < KPT; k0 += CB) {
                 uint32_t r[CB];
@@ -1415,11 +1346,10 @@ __global__ void __launch_bounds__(BK_T) bucket_scatter_lines_kernel(const T *__r
             const uint32_t gi = sgb[b] + e0;  // mod 2^32
             T *tgt = (sb.y >> 10) & 1 ? out2 : out;
             if (full) {
-                if constexpr (((DSORT_LINES_NT >> (sizeof(T) == 8 ? 1 : 0)) & 1) && !HT) {
-                    using NV = typename std::conditional<sizeof(T) == 4, bk_v4i, bk_v2l>::type;
-                    NV vv;
-                    __builtin_memcpy(&vv, v, sizeof(NV));
-                    __builtin_nontemporal_store(vv, reinterpret_cast<NV *>(tgt + gi));
+                if constexpr (sizeof(T) == 4 && !HT) {  // (non-temporal: int32 lines only, see BkIds)
+                    bk_v4i vv;
+                    __builtin_memcpy(&vv, v, sizeof(vv));
+                    __builtin_nontemporal_store(vv, reinterpret_cast<bk_v4i *>(tgt + gi));
                 } else {
                     V vv;
                     __builtin_memcpy(&vv, v, sizeof(V));

@@ -54,10 +54,8 @@ struct PassDesc {
 struct dsort_opts {
     int64_t buckets = -1;           // DSORT_OPT_BUCKETS: -1 auto, 0 off, B forced
     int64_t bucket_keys = 1 << 20;  // DSORT_OPT_BUCKET_KEYS
-#ifndef DSORT_BUCKET_OS_DEFAULT
-#define DSORT_BUCKET_OS_DEFAULT 128
-#endif
-    int64_t bucket_os = DSORT_BUCKET_OS_DEFAULT;  // DSORT_OPT_BUCKET_OVERSAMPLE
+    static constexpr int64_t BUCKET_OS_DEFAULT = 128;
+    int64_t bucket_os = BUCKET_OS_DEFAULT;  // DSORT_OPT_BUCKET_OVERSAMPLE
     int64_t max_logf = -1;          // DSORT_OPT_MAX_FANIN_LOG2: -1 = per key type default
     int64_t kill_after_pass = -1;   // DSORT_OPT_KILL_AFTER_STAGE
     int64_t stage_timing = 1;       // DSORT_OPT_STAGE_TIMING
@@ -339,7 +337,7 @@ int bx_sample(dsort_ctx *ctx, const T *d_in, const BxPlan &pl, BxSample *d_smp, 
 //    them).  *hb = this rank's bucket starts (host, Btot + 1), *part = the partitioned keys.  Kill
 //    stage 0 fires here.
 //    pure[g] (Btot): global bucket g lies between two splitters of one key.  Its keys are dropped
-//    (DSORT_BX_DROP_PURE, round 6): part holds the others at the compacted starts -- every pure
+//    (the scatter's pure-bucket drop, round 6): part holds the others at the compacted starts -- every pure
 //    bucket of size 0 -- and the owner fills a pure bucket with its key, so its keys never cross
 //    the links.
 template <typename T>

@@ -36,9 +36,6 @@ constexpr int SB_T = 256;              // threads of the per-chunk kernels
 constexpr int SB_MAXS = 1024;          // sub-buckets per bucket at most
 constexpr int SB_SLOTB = 10;           // slot table: 1024 key slots per bucket
 constexpr int SB_SLOTS = 1 << SB_SLOTB;
-#ifndef DSORT_SUB_TOTALS
-#define DSORT_SUB_TOTALS 1  // local path: sb_local_kernel adds up the sub-bucket totals (global atomics)
-#endif
 constexpr int SB_ST = 4;               // sub-tiles per chunk
 template <typename T> constexpr int SB_KPT = sizeof(T) == 4 ? 16 : 8;  // keys per thread per sub-tile
 template <typename T> constexpr int SB_SUB = SB_T * SB_KPT<T>;   // keys of a sub-tile
@@ -134,7 +131,7 @@ __device__ __forceinline__ bool below(const Spl<T> &s, T key, uint32_t pos) {
 // outer sub-bucket the (key, position) order gives it, so those stay as full as sampled; the
 // copies in between may go to any sub-bucket between the first and the last K splitter (each holds
 // only K), and a hash of the position spreads them evenly -- instead of a divergent binary search
-// (C4: second level 3.0 -> 2.3 ms).  (In proportion to the position, the first level's rule, the
+// (C4: second level 3.0 -> 2.3 ms).  (In proportion to the position, the first level's rule then, the
 // sub-buckets came out uneven -- a bucket at the edge of a heavy key's run holds that key's copies
 // from one end of the input only -- and one overflowed a tile in most sorts.)  Only this function
 // places keys on the local path; the scatter path's two passes both call it.
@@ -191,10 +188,7 @@ __device__ __forceinline__ int sub_of(const Spl<T> *spl, const uint32_t *rng, T 
 // not a multiple of 8) samples single keys.  Runs of 8 keys (round 4, at 8 samples per
 // sub-bucket): the kernel fetches a line per run, half the lines of runs of 4 (-0.05 ms per sort
 // at 2^30 int32; no over-tile sub-bucket in 24 sorts).
-#ifndef DSORT_SB_RUN
-#define DSORT_SB_RUN 8
-#endif
-constexpr uint32_t SB_RUN = DSORT_SB_RUN;
+constexpr uint32_t SB_RUN = 8;
 constexpr uint32_t SB_SMP_CH = 1024;  // chunks of a several-piece bucket staged in LDS for its sampling
 __host__ __device__ __forceinline__ uint32_t sample_run(const BInfo &b) { return b.single || b.ns % SB_RUN ? 1u : SB_RUN; }
 // (positions relative to the bucket: bucket_src_pos maps them to the source)
@@ -589,10 +583,8 @@ __global__ void __launch_bounds__(SB_MAXS, 8) sb_scan_kernel(const BInfo *__rest
         // (pref[c][0] = 0): one load per chunk instead of two
         uint32_t a = 0;
         if (j < ns) {
-#ifndef DSORT_SCAN_SUM_U
-#define DSORT_SCAN_SUM_U 16
-#endif
-#pragma unroll DSORT_SCAN_SUM_U  // (independent loads in flight: the loop is latency-bound)
+            constexpr int SCAN_SUM_U = 16;
+#pragma unroll SCAN_SUM_U  // (independent loads in flight: the loop is latency-bound)
             for (uint32_t c = b.c0; c < b.c1; ++c) a += counts[(uint64_t)c * (SS + 1) + j + 1];
             ss[j + 1] = a;
         }
@@ -638,10 +630,7 @@ __global__ void __launch_bounds__(SB_MAXS, 8) sb_scan_kernel(const BInfo *__rest
     }
     __syncthreads();
     SCST(2);
-#ifndef DSORT_SCAN_CHAIN_WAVE
-#define DSORT_SCAN_CHAIN_WAVE 1
-#endif
-    if (DSORT_SCAN_CHAIN_WAVE && j < 64) {
+    if (j < 64) {
         // the chain 0, nxt[0], nxt[nxt[0]], ... walked by wave 0 through a 64-entry window of nxt
         // held one entry per lane: a step is a lane read (readlane) instead of an LDS round trip
         // (one thread walking ~130 steps through LDS was a quarter of the kernel).  i, base, k and
@@ -667,11 +656,6 @@ __global__ void __launch_bounds__(SB_MAXS, 8) sb_scan_kernel(const BInfo *__rest
         }
         flush();
         if (lane == 0) nchain = k;
-    }
-    if (!DSORT_SCAN_CHAIN_WAVE && j == 0) {
-        int k = 0;
-        for (int i = 0; i < ns; i = nxt[i]) chain[k++] = (uint16_t)i;
-        nchain = (uint32_t)k;
     }
     __syncthreads();
     SCST(3);
@@ -732,10 +716,7 @@ __global__ void __launch_bounds__(SB_MAXS, 8) sb_scan_kernel(const BInfo *__rest
             }
         }
     }
-#ifndef DSORT_SCAN_PIECES
-#define DSORT_SCAN_PIECES 1
-#endif
-    if (LOCAL && pieces && DSORT_SCAN_PIECES) {
+    if (LOCAL && pieces) {
         // The piece tables: entry (tile t, chunk c) = chunk c's start + pref[c][bnd[t]], + pref[c][bnd[t + 1]]
         // with bnd = the chain, then ns.  A group of chunks' prefix values at the tile bounds goes to
         // LDS first: the loads run along a chunk's prefix row and the table stores along a tile's
@@ -776,22 +757,6 @@ __global__ void __launch_bounds__(SB_MAXS, 8) sb_scan_kernel(const BInfo *__rest
                 if (tix[t] == 0xFFFF || k >= tcap) continue;  // (the host sees ntiles > tcap and fails the sort)
                 const uint32_t bs = pbs[c];
                 pieces[(uint64_t)k * PS + g0 + c] = make_uint2(bs + pv[c * nb + t], bs + pv[c * nb + t + 1]);
-            }
-        }
-    }
-    if (LOCAL && pieces && !DSORT_SCAN_PIECES) {
-        __syncthreads();
-        // the piece tables: a wave per tile, a lane per chunk (no division per entry)
-        const uint32_t nch = b.c1 - b.c0, lane = threadIdx.x & 63;
-        for (uint32_t t = threadIdx.x >> 6; t < (uint32_t)nc; t += blockDim.x >> 6) {
-            if (tix[t] == 0xFFFF) continue;
-            const uint32_t k = tbase + tix[t];
-            if (k >= tcap) continue;  // (the host sees ntiles > tcap and fails the sort)
-            const uint32_t a0 = chain[t], a1 = nxt[a0];
-            for (uint32_t c = lane; c < nch; c += 64) {
-                const uint32_t *pc = counts + (uint64_t)(b.c0 + c) * (SS + 1);
-                const uint32_t base = (uint32_t)ch[b.c0 + c].start;
-                pieces[(uint64_t)k * PS + c] = make_uint2(base + pc[a0], base + pc[a1]);
             }
         }
     }
@@ -836,30 +801,17 @@ __device__ __forceinline__ uint32_t sb_chunk_order(uint32_t bid, uint32_t G) {
 
 // int32: 1024 threads of 15 keys, 8 waves per SIMD at two workgroups per CU: twice the waves of
 // round 2's 512 threads of 31 keys to hide the lookups' LDS round trips (2.33 -> 2.02 ms at 2^30).
-// int64 (round 6): 1024 threads of 6 keys, lookups in pairs (DSORT_SB_G64) -- round 5 measured this
+// int64 (round 6): 1024 threads of 6 keys, lookups in pairs (SB_G64) -- round 5 measured this
 // geometry with 8-key batches, which spilled 22 VGPRs at 8 waves per SIMD (C4 +0.9 ms,
 // profiles/r5_ab_c4_local_1024x6.log); in pairs nothing spills, and since the first level's one-key
 // hash (dsort_bucket.h bucket_onekey) C4's buckets hold hardly any duplicate run: C4 second level
 // 2.21 -> 1.82 ms, uniform int64 3.78 -> 3.48 ms (profiles/r6_ab_local_partition_i64_1024x6.log;
 // 512 x 13 with 8-key batches before)
-#ifndef DSORT_SB_LT32
-#define DSORT_SB_LT32 1024
-#endif
-#ifndef DSORT_SB_KPT32
-#define DSORT_SB_KPT32 15
-#endif
-#ifndef DSORT_SB_G32
-#define DSORT_SB_G32 1  // int32 keys per batch of the classify (G below)
-#endif
-#ifndef DSORT_SB_LT64
-#define DSORT_SB_LT64 1024
-#endif
-#ifndef DSORT_SB_KPT64
-#define DSORT_SB_KPT64 6
-#endif
-template <typename T> constexpr int SB_LT = sizeof(T) == 4 ? DSORT_SB_LT32 : DSORT_SB_LT64;
+constexpr int SB_LT32 = 1024, SB_KPT32 = 15, SB_LT64 = 1024, SB_KPT64 = 6;
+constexpr int SB_G32 = 1, SB_G64 = 2;  // keys per batch of the classify (G below)
+template <typename T> constexpr int SB_LT = sizeof(T) == 4 ? SB_LT32 : SB_LT64;
 // keys per thread: the chunk (int32 60 KiB, int64 48 KiB) + tables fit two workgroups per CU
-template <typename T> constexpr int SB_LKPT = sizeof(T) == 4 ? DSORT_SB_KPT32 : DSORT_SB_KPT64;
+template <typename T> constexpr int SB_LKPT = sizeof(T) == 4 ? SB_KPT32 : SB_KPT64;
 
 template <typename T> constexpr int SB_LCH = SB_LT<T> * SB_LKPT<T>;
 
@@ -931,10 +883,7 @@ __global__ void __launch_bounds__(SB_LT<T>, SB_LT<T> / 128) sb_local_kernel(T *_
     // In groups of G keys: the slot-table reads, then the splitter reads, then the atomics, so a
     // key's LDS round trips do not wait for the previous key's.  A key past the chunk adds 0.
     // (int32: 31 keys and their ranks are already live; batching spills and measured slower)
-#ifndef DSORT_SB_G64
-#define DSORT_SB_G64 2
-#endif
-    constexpr int G = sizeof(T) == 4 ? DSORT_SB_G32 : DSORT_SB_G64;
+    constexpr int G = sizeof(T) == 4 ? SB_G32 : SB_G64;
     // a whole chunk: only the first and last slot rows can fall outside it
     const bool whole = c.len == (uint32_t)CHL;
     if constexpr (G == 1) {

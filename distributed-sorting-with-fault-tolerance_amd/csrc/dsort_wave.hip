@@ -68,11 +68,9 @@ template <typename T> struct WG;
 // int32 tile sort: 8192-key tiles of 512 threads, four workgroups per CU (40 KiB of LDS each):
 // while one workgroup gathers its tile another sorts (16384-key tiles, two per CU: bin sort 2.47
 // -> 2.05 ms at 2^30; round 4).
-#ifndef DSORT_I32_WAVES
-#define DSORT_I32_WAVES 8
-#endif
+constexpr int I32_WAVES = 8;
 template <> struct WG<int32_t> {
-    static constexpr int WAVES = DSORT_I32_WAVES, MWAVES = 16, OCC = 8, MAXLOGF = 5;
+    static constexpr int WAVES = I32_WAVES, MWAVES = 16, OCC = 8, MAXLOGF = 5;
 };
 template <> struct WG<int64_t> {
     // F = 32 would need 32 run heads of 64-bit keys per lane next to the window: it spills, so
@@ -742,13 +740,10 @@ __device__ __forceinline__ void window_pass(T *s, int P, int tid) {
     for (int q = 0; q < 16 / N; ++q) *p[q] = V16<T>::make(v + N * q);
 }
 
-// The tile sort's output as non-temporal stores (round 6, int32: bit 0; int64 bit 1): 2^30 int32
+// The tile sort's output as non-temporal stores (round 6, both key widths): 2^30 int32
 // 7.56 -> 7.50 ms of device time over 3 of 3 interleaved runs; 2^30 uniform int64 16.43 -> 16.21 ms
 // (3 of 3), C4 neutral; the local partition's in-place write-back the same way measured neutral
 // (profiles/r6_ab_nontemporal_tile_out.log, r6_ab_nontemporal_i64.log).
-#ifndef DSORT_TILE_OUT_NT
-#define DSORT_TILE_OUT_NT 3
-#endif
 // Bin sort of one tile held in x (slots past `valid` are key_max) into out[0, valid).
 //   1. range [mn, mx] of the keys below key_max (they and the padding are not binned: the output
 //      ends with valid - M of them, M = the binned keys);
@@ -916,14 +911,10 @@ __device__ __forceinline__ bool bin_sort_tile(const T (&x)[R], int valid, T *s, 
             const int p0 = N * q;
             const V v = *reinterpret_cast<const V *>(s + bsw<T>((uint32_t)p0));
             if (p0 >= sh && p0 + N <= E) {
-                if constexpr ((DSORT_TILE_OUT_NT >> (sizeof(T) == 8 ? 1 : 0)) & 1) {
-                    using NV = typename std::conditional<sizeof(T) == 4, bk::bk_v4i, bk::bk_v2l>::type;
-                    NV nv;
-                    __builtin_memcpy(&nv, &v, sizeof(NV));
-                    __builtin_nontemporal_store(nv, reinterpret_cast<NV *>(ob + p0));
-                } else {
-                    *reinterpret_cast<V *>(ob + p0) = v;
-                }
+                using NV = typename std::conditional<sizeof(T) == 4, bk::bk_v4i, bk::bk_v2l>::type;
+                NV nv;
+                __builtin_memcpy(&nv, &v, sizeof(NV));
+                __builtin_nontemporal_store(nv, reinterpret_cast<NV *>(ob + p0));
             } else {
                 T k[N];
                 V16<T>::get(v, k);
@@ -972,11 +963,8 @@ __device__ __forceinline__ void gather_pieces(const sb::Gather &ga, uint32_t jt,
         pe[q] = k < ga.PS ? ga.pieces[(uint64_t)jt * ga.PS + k] : make_uint2(0u, 0u);
     }
 }
-// ptab: 3 kMaxPieces + 1 words of LDS for the piece table, then (DSORT_GATHER_VPC) TILE / N 16-bit
-// piece indices of the vector slots; wsum: one word per wave.
-#ifndef DSORT_GATHER_VPC
-#define DSORT_GATHER_VPC 1
-#endif
+// ptab: 3 kMaxPieces + 1 words of LDS for the piece table, then TILE / N 16-bit piece indices of
+// the vector slots (small pieces, `vp` below); wsum: one word per wave.
 template <typename T, int W>
 __device__ __forceinline__ void gather_tile(const sb::Gather &ga, const uint2 (&pe)[2], const sb::GTile &gt,
                                             const T *in, uint32_t *ptab, uint32_t *wsum, T (&x)[R],
@@ -1012,7 +1000,7 @@ __device__ __forceinline__ void gather_tile(const sb::Gather &ga, const uint2 (&
         ex += i < w ? v : 0;
         tot += v;
     }
-    // DSORT_GATHER_VPC (round 6): with small pieces (under 20 vectors on average: a C3 rank's tiles
+    // Round 6: with small pieces (under 20 vectors on average: a C3 rank's tiles
     // gather 273 pieces of ~60 int32 keys) the piece of every vector slot (16-bit, behind the piece
     // table), written by the piece's thread -- a lane's loads then look their piece up with one read
     // each, independently, where the walk up the pieces (a binary search for the first, then a step
@@ -1020,7 +1008,7 @@ __device__ __forceinline__ void gather_tile(const sb::Gather &ga, const uint2 (&
     // up to ~25 round trips in front of the last load.  C3 rank: tile sort 1.51 -> 1.38 ms; with the
     // one-GPU sort's ~30-vector pieces the fill cost more than the walk (+0.04 ms), so those walk
     // (profiles/r6_ab_gather_vpc.log).  Workgroup-uniform.
-    const bool vp = DSORT_GATHER_VPC && !keyw && tot < 20u * (uint32_t)np;
+    const bool vp = !keyw && tot < 20u * (uint32_t)np;
     uint16_t *vpc = reinterpret_cast<uint16_t *>(phi + KP);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -1224,13 +1212,10 @@ __global__ void __launch_bounds__(64 * W, WG<T>::OCC) bin_sort_kernel(const T *i
         const auto *bs = static_cast<const typename bk::Comp<T>::C *>(ga.bspl);
         const bool lk = gt.j0 > 0 || gt.b > 0, hk = gt.j1 < gt.nsub || (int)gt.b + 1 < ga.B;
         known = lk && hk;
-        // int32 (DSORT_LATE_BOUNDS): the bounds and the duplicate hint are read after the key loads
+        // int32 (late bounds): the bounds and the duplicate hint are read after the key loads
         // are issued -- read here, their round trip sat between the tile record and the key loads
         // (one of the gather's four dependent round trips); int64 needs them first (one-key tiles)
-#ifndef DSORT_LATE_BOUNDS
-#define DSORT_LATE_BOUNDS 1
-#endif
-        constexpr bool late = DSORT_LATE_BOUNDS && sizeof(T) == 4;
+        constexpr bool late = sizeof(T) == 4;
         const int jl = gt.j0 > 0 ? (int)gt.j0 - 1 : 0, jh = (int)gt.j1 - 1;  // splitters around the tile
         const int nspl = (int)gt.nsub - 1;
         const int jj = jl + lane_id();
@@ -1246,10 +1231,7 @@ __global__ void __launch_bounds__(64 * W, WG<T>::OCC) bin_sort_kernel(const T *i
         if (!late && known) {
             klo = gt.j0 > 0 ? sp[gt.j0 - 1].k : bk::Comp<T>::key_of(bs[gt.b - 1]);
             khi = gt.j1 < gt.nsub ? sp[gt.j1 - 1].k : bk::Comp<T>::key_of(bs[gt.b]);
-#ifndef DSORT_ONEKEY_TILES
-#define DSORT_ONEKEY_TILES 1
-#endif
-            if (DSORT_ONEKEY_TILES && sizeof(T) == 8 && klo == khi) {
+            if (sizeof(T) == 8 && klo == khi) {
                 // Bounds of one key: every key of the tile is that key (the sub-buckets of a heavy
                 // duplicate, int64 Zipf's keys with thousands of copies) -- the tile is written as
                 // its key, without reading it.  (The first level does the same for pure buckets.)
@@ -1596,6 +1578,13 @@ static int stage_event(dsort_ctx *ctx, hipStream_t s, bool timed, int i) {
 static int tile_sort_event(dsort_ctx *ctx, hipStream_t s, bool timed, int which) {
     return stage_event(ctx, s, timed, 7 + which);
 }
+// The last event of a timed sort (ctx->ev_done: the bucket exchange's waves move it).
+static int sort_done_event(dsort_ctx *ctx, hipStream_t s, bool timed) {
+    if (!timed || !ctx->ev_ok) return DSORT_OK;
+    DSORT_HIP(ctx, hipEventRecord(ctx->ev[ctx->ev_done], s));
+    ctx->ev_mask |= 1u << ctx->ev_done;
+    return DSORT_OK;
+}
 
 // The tile sort of `grid` tiles (an upper bound when the count lives on the device): the bin
 // sort first, then the bitonic sort of the tiles it declined.  Events 7 / 8 around both.
@@ -1748,10 +1737,7 @@ static int wave_merge(dsort_ctx *ctx, const T *d_in, const size_t *lens, int k, 
 
 // ---- second partition level (dsort_sub.h) -------------------------------------------------
 // Nominal keys per sub-bucket: TILE / 8 unless DSORT_OPT_SUB_KEYS says otherwise (0 = off).
-#ifndef DSORT_SUB_NOM_16THS
-#define DSORT_SUB_NOM_16THS 3
-#endif
-constexpr uint64_t SUB_NOM_16THS = DSORT_SUB_NOM_16THS;  // nominal sub-bucket: 3/16 of a tile
+constexpr uint64_t SUB_NOM_16THS = 3;  // nominal sub-bucket: 3/16 of a tile
 template <typename T>
 static uint64_t sub_keys(const dsort_opts &opt) {
     const int64_t v = opt.sub_keys;
@@ -1879,11 +1865,105 @@ __global__ void __launch_bounds__(256) fill_segments_kernel(T *out, const FillSe
     }
 }
 
+// What a caller hands to sub_sort; the retry after a tile-table overflow runs on the same.
 template <typename T>
-static int sub_sort(dsort_ctx *ctx, T *src, T *d_keys, uint64_t n, const uint64_t *hb, int B, uint64_t m_in,
-                    hipStream_t s, bool timed, bool local, const uint8_t *pure, bool pure_done, const void *bspl,
-                    bool retry = false, const PieceMap<T> *pm = nullptr, const T *fill_keys = nullptr) {
+struct SubArgs {
+    T *src, *d_keys;
+    uint64_t n;
+    const uint64_t *hb;     // the bucket starts (host, B + 1)
+    int B;
+    hipStream_t s;
+    bool timed;
+    const uint8_t *pure;    // B: a bucket of one key, which the second level skips
+    bool pure_done;         // the first level put the pure buckets in d_keys (or dropped them: fill_keys)
+    const void *bspl;       // the first level's splitters (device)
+    const PieceMap<T> *pm;  // where the buckets lie in src (nullptr: at hb)
+    const T *fill_keys;     // B: the keys of the pure buckets that the first-level scatter dropped
+};
+
+// The second level's plan: host arithmetic only (sub_plan).
+template <typename T>
+struct SubPlan {
+    int TILE;         // keys per tile: TILE_OF<T> or (int32, large buckets) TILE_W<16>
+    uint64_t m;       // nominal sub-bucket
+    int os;           // samples per sub-bucket
+    bool local;       // the local (gather) path, else the scatter path
+    bool fell_back;   // local was asked for and is not possible (pieces, source alignment)
+    uint64_t CH;      // keys per chunk
+    std::vector<sb::BInfo> bi;
+    uint64_t nsmp, nch, nsubs;  // samples, chunks, sub-buckets in all
+    int SS;           // sub-buckets of a bucket at most, a multiple of 64: the tables' stride
+    uint32_t PS;      // local: the piece tables' stride (most chunks of a bucket)
+    uint64_t tcap;    // local: a bound on the tiles (the piece tables' rows)
+    uint64_t tmax;    // rows of the tile table
+    bool totals;      // local: sb_local_kernel adds up the sub-bucket totals (SubArena.stot)
+    uint64_t npure;   // keys in pure buckets
+    std::vector<FillSeg<T>> fill;  // pure buckets written as their key
+    uint64_t maxfill;              // the longest of them
+    std::vector<bk::TileRef> stl;  // the sample tiles: every bucket's samples
+    size_t arena_bytes;
+};
+
+// The second level's device tables (ctx->sub), every one at the next 256-byte boundary, and the
+// pinned pair of counters read back.
+template <typename T>
+struct SubArena {
+    sb::BInfo *bi;
+    sb::Chunk *ch;
+    T *smp;
+    int64_t *cmp, *srt;
+    sb::Spl<T> *spl;
+    uint32_t *rng;
+    sb::SlotFn<T> *sfn;
+    uint32_t *cnt, *offs;
+    void *tt;          // GTile (local) or TileRef (scatter)
+    sb::Ovf *ovf;
+    uint32_t *num;     // tiles, merge records
+    bk::TileRef *stl;  // sample tiles, then their count
+    uint2 *pcs;        // local path: piece tables
+    FillSeg<T> *fill;
+    uint32_t *stot;    // sub-bucket totals (SubPlan.totals), else null
+    uint32_t *hn;      // pinned: num as the host reads it back (sub_stage)
+};
+// The tables from `base` on; returns their bytes (base 0: the size alone).
+template <typename T>
+static size_t sub_arena(const SubArgs<T> &a, const SubPlan<T> &p, uintptr_t base, SubArena<T> &A) {
     using namespace sb;
+    const size_t B = (size_t)a.B, SS = (size_t)p.SS;
+    uintptr_t at = base;
+    auto take = [&](auto *&ptr, size_t bytes) {
+        ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(at);
+        at += (bytes + 255) & ~(size_t)255;
+    };
+    take(A.bi, B * sizeof(BInfo));
+    take(A.ch, p.nch * sizeof(Chunk));
+    take(A.smp, p.nsmp * sizeof(T));
+    take(A.cmp, p.nsmp * 8);
+    take(A.srt, sizeof(T) == 8 ? p.nsmp * 8 : 0);
+    take(A.spl, B * SS * sizeof(Spl<T>));
+    take(A.rng, B * SB_SLOTS * 4);
+    take(A.sfn, B * sizeof(SlotFn<T>));
+    take(A.cnt, p.nch * (SS + 1) * 4);
+    take(A.offs, p.local ? 0 : p.nch * SS * 4);
+    take(A.tt, p.tmax * sizeof(GTile));
+    take(A.ovf, p.nsubs * sizeof(Ovf));
+    take(A.num, 8);
+    take(A.stl, B * sizeof(bk::TileRef) + 16);
+    take(A.pcs, p.local ? p.tcap * p.PS * sizeof(uint2) : 0);
+    take(A.fill, a.pm || a.fill_keys ? B * sizeof(FillSeg<T>) : 0);
+    take(A.stot, p.totals ? B * SS * 4 : 0);
+    if (!p.totals) A.stot = nullptr;
+    return at - base;
+}
+
+template <typename T>
+static SubPlan<T> sub_plan(const dsort_opts &opt, const SubArgs<T> &a, uint64_t m_in, bool local, bool retry) {
+    using namespace sb;
+    const int B = a.B;
+    const uint64_t *hb = a.hb;
+    const uint8_t *pure = a.pure;
+    const PieceMap<T> *pm = a.pm;
+    SubPlan<T> p;
     // The tile: int32 buckets above 2M keys take 16384-key tiles -- their sub-buckets (at most
     // SB_MAXS per bucket) would average above a quarter of an 8192-key tile, and sampled 8 per
     // sub-bucket many would overflow it (a 2^29-key rank of C3 has 4M-key buckets: 115 ms of split
@@ -1893,8 +1973,7 @@ static int sub_sort(dsort_ctx *ctx, T *src, T *d_keys, uint64_t n, const uint64_
     for (int b = 0; b < B; ++b)
         if (!pure[b]) maxlen = std::max<uint64_t>(maxlen, hb[b + 1] - hb[b]);
     const int TILE = sizeof(T) == 4 && maxlen > (uint64_t)SB_MAXS * TILE_OF<T> / 4 ? TILE_W<16> : TILE_OF<T>;
-    const uint64_t m = ctx->opt.sub_keys < 0 && TILE != TILE_OF<T> ? (uint64_t)TILE / 8 : m_in;
-    ctx->stats.tile_keys = TILE;
+    const uint64_t m = opt.sub_keys < 0 && TILE != TILE_OF<T> ? (uint64_t)TILE / 8 : m_in;
     constexpr uint64_t ALIGN = KPC<T>;
     const bool asked_local = local;
     const uint64_t LCH = SB_LCH<T>;
@@ -1908,26 +1987,24 @@ static int sub_sort(dsort_ctx *ctx, T *src, T *d_keys, uint64_t n, const uint64_
     };
     for (int b = 0; b < B && local; ++b)
         if (bucket_chunks(b, LCH) > (uint64_t)kMaxPieces<T>) local = false;
-    if (reinterpret_cast<uintptr_t>(src) % 16) local = false;  // (the gather reads aligned 16-byte vectors)
-    if (asked_local && !local) ctx->stats.sub_scatter_fallback = 1;
+    if (reinterpret_cast<uintptr_t>(a.src) % 16) local = false;  // (the gather reads aligned 16-byte vectors)
     const uint64_t CH = local ? SB_LCH<T> : SB_CH<T>;
     // samples per sub-bucket; a bucket's samples (<= SB_MAXS * 8) fit one int64 tile
     constexpr int kMaxOs = TILE_OF<int64_t> / SB_MAXS;
     // (nominal sub-buckets above an eighth of a tile -- the default 3/16 -- sample at the maximum
     // rate: at 4 samples 10 of 16 sorts of 2^30 int32 met a sub-bucket above a tile, each costing
     // 0.1-0.7 ms of split merge)
-    int os = ctx->opt.sub_os > 0 ? (ctx->opt.sub_os < kMaxOs ? (int)ctx->opt.sub_os : kMaxOs)
-                                 : (m > (uint64_t)TILE / 8 ? kMaxOs : 4);
+    int os = opt.sub_os > 0 ? (opt.sub_os < kMaxOs ? (int)opt.sub_os : kMaxOs) : (m > (uint64_t)TILE / 8 ? kMaxOs : 4);
     // buckets so large that even SB_MAXS sub-buckets average above the nominal size (and above an
     // eighth of a tile): sample at the maximum rate, so the size spread (about 1/sqrt(os)) keeps
     // every sub-bucket below a tile
     // (at a quarter tile and os = 4, about one sort in 30 of two 3.3M-key buckets met a sub-bucket
     // above a tile and took the scatter path)
-    if (ctx->opt.sub_os <= 0)
+    if (opt.sub_os <= 0)
         for (int b = 0; b < B; ++b)
             if (!pure[b] && hb[b + 1] - hb[b] > (uint64_t)SB_MAXS * std::max<uint64_t>(m, TILE / 8)) os = kMaxOs;
     // bucket and chunk tables
-    std::vector<BInfo> bi((size_t)B);
+    p.bi.resize((size_t)B);
     uint64_t nsmp = 0, nch = 0, nsubs = 0;
     int SS = 1;
     // local path: the piece tables' stride (most chunks of a bucket) and a bound on the tiles -- a
@@ -1949,55 +2026,69 @@ static int sub_sort(dsort_ctx *ctx, T *src, T *d_keys, uint64_t n, const uint64_
             const uint64_t room = (uint64_t)TILE - 2 * (ALIGN - 1) * nc;
             tcap += 2 * len / room + 1 + 8 + (2 * m > room ? ns : 0);
         }
-        bi[b] = BInfo{hb[b], nsmp, (uint32_t)len, (uint32_t)ns, ns > 1 ? (uint32_t)(ns * os) : 0u, (uint32_t)nch,
-                      (uint32_t)(nch + nc), retry ? 1u : 0u, pm ? 1u : 0u};
-        nsmp += bi[b].ns;
+        p.bi[b] = BInfo{hb[b], nsmp, (uint32_t)len, (uint32_t)ns, ns > 1 ? (uint32_t)(ns * os) : 0u, (uint32_t)nch,
+                        (uint32_t)(nch + nc), retry ? 1u : 0u, pm ? 1u : 0u};
+        nsmp += p.bi[b].ns;
         nch += nc;
         nsubs += ns;
         SS = (int)ns > SS ? (int)ns : SS;
     }
     SS = (SS + 63) & ~63;
-    if (ctx->opt.test_tile_cap > 0) tcap = std::min<uint64_t>(tcap, (uint64_t)ctx->opt.test_tile_cap);
+    if (opt.test_tile_cap > 0) tcap = std::min<uint64_t>(tcap, (uint64_t)opt.test_tile_cap);
+    p.TILE = TILE;
+    p.m = m;
+    p.os = os;
+    p.local = local;
+    p.fell_back = asked_local && !local;
+    p.CH = CH;
+    p.nsmp = nsmp;
+    p.nch = nch;
+    p.nsubs = nsubs;
+    p.SS = SS;
+    p.PS = PS;
+    p.tcap = tcap;
+    // tiles, bound (sb_scan_kernel); the local path's split tiles: tcap
+    p.tmax = std::max<uint64_t>(nsubs + ceil_div(a.n, TILE) + (uint64_t)B, local ? tcap : 0);
     // local path, int32: the sub-bucket totals added up by sb_local_kernel's atomics (sb_scan 126 -> 91 us,
     // sb_local +10 us at 2^30); int64 sums the prefix rows in sb_scan (C4: the atomics cost sb_local
     // about as much as they saved, profiles/r5_ab_sub_scan.log)
-    constexpr bool SUB_TOTALS = DSORT_SUB_TOTALS && sizeof(T) == 4;
-    // tiles, bound (sb_scan_kernel); the local path's split tiles: tcap
-    const uint64_t tmax = std::max<uint64_t>(nsubs + ceil_div(n, TILE) + (uint64_t)B, local ? tcap : 0);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_bi = take(B * sizeof(BInfo)), o_ch = take(nch * sizeof(Chunk)), o_smp = take(nsmp * sizeof(T)),
-                 o_cmp = take(nsmp * 8), o_srt = take(sizeof(T) == 8 ? nsmp * 8 : 0),
-                 o_spl = take((size_t)B * SS * sizeof(Spl<T>)),
-                 o_rng = take((size_t)B * SB_SLOTS * 4), o_sfn = take(B * sizeof(SlotFn<T>)),
-                 o_cnt = take(nch * (SS + 1) * 4), o_offs = take(local ? 0 : nch * SS * 4),
-                 o_tt = take(tmax * sizeof(GTile)),
-                 o_ovf = take(nsubs * sizeof(Ovf)), o_num = take(8), o_stl = take(B * sizeof(bk::TileRef) + 16),
-                 o_pcs = take(local ? tcap * PS * sizeof(uint2) : 0),
-                 o_fill = take(pm || fill_keys ? B * sizeof(FillSeg<T>) : 0),
-                 o_tot = take(local && SUB_TOTALS ? (size_t)B * SS * 4 : 0);
-    int rc = ensure(ctx, &ctx->sub, &ctx->sub_bytes, off, "sub-bucket partition");
+    p.totals = local && sizeof(T) == 4;
+    // pure buckets of a piece map, or whose keys the first-level scatter dropped (fill_keys): their
+    // one key written over their output range
+    p.npure = p.maxfill = 0;
+    for (int b = 0; b < B; ++b) {
+        if (!pure[b]) continue;
+        const uint64_t len = hb[b + 1] - hb[b];
+        p.npure += len;
+        if ((pm || a.fill_keys) && len) {
+            p.fill.push_back(FillSeg<T>{hb[b], len, pm ? pm->pure_key[b] : a.fill_keys[b]});
+            p.maxfill = std::max(p.maxfill, len);
+        }
+    }
+    for (int b = 0; b < B; ++b)
+        if (p.bi[b].ns) p.stl.push_back(bk::TileRef{p.bi[b].soff, p.bi[b].ns, 0});
+    SubArena<T> none;
+    p.arena_bytes = sub_arena<T>(a, p, 0, none);
+    return p;
+}
+
+// Staging: the arena, and the pinned tables -- buckets, chunks (with or without a piece map),
+// sample tiles, fill segments -- uploaded on the side stream; the sort stream waits for them.
+template <typename T>
+static int sub_stage(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T> &p, SubArena<T> &A) {
+    using namespace sb;
+    const size_t B = (size_t)a.B;
+    const uint64_t CH = p.CH, nch = p.nch;
+    const PieceMap<T> *pm = a.pm;
+    const std::vector<BInfo> &bi = p.bi;
+    int rc = ensure(ctx, &ctx->sub, &ctx->sub_bytes, p.arena_bytes, "sub-bucket partition");
     if (rc) return rc;
-    char *a = static_cast<char *>(ctx->sub);
-    BInfo *dbi = reinterpret_cast<BInfo *>(a + o_bi);
-    Chunk *dch = reinterpret_cast<Chunk *>(a + o_ch);
-    T *smp = reinterpret_cast<T *>(a + o_smp);
-    int64_t *cmp = reinterpret_cast<int64_t *>(a + o_cmp), *srt = reinterpret_cast<int64_t *>(a + o_srt);
-    Spl<T> *spl = reinterpret_cast<Spl<T> *>(a + o_spl);
-    uint32_t *rng = reinterpret_cast<uint32_t *>(a + o_rng);
-    SlotFn<T> *sfn = reinterpret_cast<SlotFn<T> *>(a + o_sfn);
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(a + o_cnt), *offs = reinterpret_cast<uint32_t *>(a + o_offs);
-    void *tt = a + o_tt;  // GTile (local) or TileRef (scatter)
-    Ovf *ovf = reinterpret_cast<Ovf *>(a + o_ovf);
-    uint32_t *num = reinterpret_cast<uint32_t *>(a + o_num);  // tiles, merge records
-    bk::TileRef *stl = reinterpret_cast<bk::TileRef *>(a + o_stl);  // sample tiles, then their count
-    uint2 *pcs = reinterpret_cast<uint2 *>(a + o_pcs);                // local path: piece tables
-    uint32_t *stot = local && SUB_TOTALS ? reinterpret_cast<uint32_t *>(a + o_tot) : nullptr;  // sub-bucket totals
+    sub_arena<T>(a, p, reinterpret_cast<uintptr_t>(ctx->sub), A);
     // pinned staging: the two tables, the sample tiles + count, then the two counters read back
     const size_t h_ch = (B * sizeof(BInfo) + 15) & ~(size_t)15, h_stl = h_ch + nch * sizeof(Chunk);
     const size_t h_num = h_stl + B * sizeof(bk::TileRef) + 16;
     const size_t h_fill = h_num + 16;
-    const size_t hbytes = h_fill + (pm || fill_keys ? B * sizeof(FillSeg<T>) : 0);
+    const size_t hbytes = h_fill + (pm || a.fill_keys ? B * sizeof(FillSeg<T>) : 0);
     if (!ctx->sub_ev && hipEventCreateWithFlags(&ctx->sub_ev, hipEventDisableTiming) != hipSuccess)
         return set_err(ctx, DSORT_EHIP, "hipEventCreate");
     if (int rc_ = sync_event(ctx, ctx->sub_ev, "tile count")) return rc_;  // the previous call's read-back is done with the staging
@@ -2009,9 +2100,10 @@ static int sub_sort(dsort_ctx *ctx, T *src, T *d_keys, uint64_t n, const uint64_
         ctx->sub_host_bytes = hbytes;
     }
     char *h = static_cast<char *>(ctx->sub_host);
+    A.hn = reinterpret_cast<uint32_t *>(h + h_num);
     std::memcpy(h, bi.data(), B * sizeof(BInfo));
     Chunk *hc = reinterpret_cast<Chunk *>(h + h_ch);
-    for (int b = 0; b < B; ++b) {
+    for (size_t b = 0; b < B; ++b) {
         if (!bi[b].len) continue;
         if (!pm) {
             for (uint64_t o = 0; o < bi[b].len; o += CH)
@@ -2027,47 +2119,47 @@ static int sub_sort(dsort_ctx *ctx, T *src, T *d_keys, uint64_t n, const uint64_
             boff -= ceil_div(pc.len, CH) * CH - pc.len;  // (the last chunk of a piece may be short)
         }
     }
-    // pure buckets of a piece map, or whose keys the first-level scatter dropped (fill_keys): their
-    // one key written over their output range
-    FillSeg<T> *hf = reinterpret_cast<FillSeg<T> *>(h + h_fill);
-    uint32_t nfill = 0;
-    uint64_t maxfill = 0;
-    for (int b = 0; (pm || fill_keys) && b < B; ++b)
-        if (pure[b] && hb[b + 1] > hb[b]) {
-            hf[nfill++] = FillSeg<T>{hb[b], hb[b + 1] - hb[b], pm ? pm->pure_key[b] : fill_keys[b]};
-            maxfill = std::max(maxfill, hb[b + 1] - hb[b]);
-        }
+    const size_t nfill = p.fill.size(), nst = p.stl.size();
+    if (nfill) std::memcpy(h + h_fill, p.fill.data(), nfill * sizeof(FillSeg<T>));
     bk::TileRef *hst = reinterpret_cast<bk::TileRef *>(h + h_stl);
-    uint32_t nst = 0;
-    for (int b = 0; b < B; ++b)
-        if (bi[b].ns) hst[nst++] = bk::TileRef{bi[b].soff, bi[b].ns, 0};
-    *reinterpret_cast<uint32_t *>(hst + B) = nst;
+    if (nst) std::memcpy(hst, p.stl.data(), nst * sizeof(bk::TileRef));
+    *reinterpret_cast<uint32_t *>(hst + B) = (uint32_t)nst;
     // The tables go up on a side stream, so the copies run while the first-level scatter (queued
     // on s before this point) is still running; s waits for them before the first kernel that
     // reads them.  (On s they queued behind the scatter: about 60 us of idle GPU per sort at 2^30.)
     // Nothing still reads the arena: the host got here after waiting for the histogram of this
     // sort, which follows every kernel of the previous sort on s.
     if ((rc = side_stream(ctx))) return rc;
-    DSORT_HIP(ctx, hipMemcpyAsync(dbi, h, B * sizeof(BInfo), hipMemcpyHostToDevice, ctx->side));
-    if (nch) DSORT_HIP(ctx, hipMemcpyAsync(dch, h + h_ch, nch * sizeof(Chunk), hipMemcpyHostToDevice, ctx->side));
-    DSORT_HIP(ctx, hipMemcpyAsync(stl, hst, B * sizeof(bk::TileRef) + 16, hipMemcpyHostToDevice, ctx->side));
-    DSORT_HIP(ctx, hipMemsetAsync(num, 0, 8, ctx->side));
+    DSORT_HIP(ctx, hipMemcpyAsync(A.bi, h, B * sizeof(BInfo), hipMemcpyHostToDevice, ctx->side));
+    if (nch) DSORT_HIP(ctx, hipMemcpyAsync(A.ch, h + h_ch, nch * sizeof(Chunk), hipMemcpyHostToDevice, ctx->side));
+    DSORT_HIP(ctx, hipMemcpyAsync(A.stl, hst, B * sizeof(bk::TileRef) + 16, hipMemcpyHostToDevice, ctx->side));
+    DSORT_HIP(ctx, hipMemsetAsync(A.num, 0, 8, ctx->side));
     if (nfill)
-        DSORT_HIP(ctx, hipMemcpyAsync(a + o_fill, hf, nfill * sizeof(FillSeg<T>), hipMemcpyHostToDevice, ctx->side));
+        DSORT_HIP(ctx, hipMemcpyAsync(A.fill, h + h_fill, nfill * sizeof(FillSeg<T>), hipMemcpyHostToDevice, ctx->side));
     DSORT_HIP(ctx, hipEventRecord(ctx->side_ev, ctx->side));
-    DSORT_HIP(ctx, hipStreamWaitEvent(s, ctx->side_ev, 0));
-    uint64_t npure = 0;
-    for (int b = 0; b < B; ++b) npure += pure[b] ? hb[b + 1] - hb[b] : 0;
-    ctx->stats.tile_sort_keys = n - npure;
+    DSORT_HIP(ctx, hipStreamWaitEvent(a.s, ctx->side_ev, 0));
+    ctx->stats.tile_sort_keys = a.n - p.npure;
+    return DSORT_OK;
+}
+
+// Pure buckets (one key) to the output, then step 1: the splitters of every other bucket.
+template <typename T>
+static int sub_splitters(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T> &p, const SubArena<T> &A) {
+    using namespace sb;
+    const int B = a.B;
+    const uint64_t *hb = a.hb;
+    const uint8_t *pure = a.pure;
+    hipStream_t s = a.s;
+    int rc;
     // pure buckets (one key) to the output as they lie, runs of them in one copy (unless the
     // scatter wrote them there); a piece map's pure buckets are filled with their key
-    if (nfill) {
-        const unsigned gx = (unsigned)std::min<uint64_t>(ceil_div(maxfill, 256 * FILL_U * (16 / sizeof(T))), 1024);
-        hipLaunchKernelGGL(fill_segments_kernel<T>, dim3(gx, nfill), dim3(256), 0, s, d_keys,
-                           reinterpret_cast<const FillSeg<T> *>(a + o_fill));
+    if (const uint32_t nfill = (uint32_t)p.fill.size()) {
+        const unsigned gx = (unsigned)std::min<uint64_t>(ceil_div(p.maxfill, 256 * FILL_U * (16 / sizeof(T))), 1024);
+        hipLaunchKernelGGL(fill_segments_kernel<T>, dim3(gx, nfill), dim3(256), 0, s, a.d_keys,
+                           static_cast<const FillSeg<T> *>(A.fill));
         DSORT_HIP(ctx, hipGetLastError());
     }
-    for (int b = 0; b < B && !pure_done && !pm;) {
+    for (int b = 0; b < B && !a.pure_done && !a.pm;) {
         if (!pure[b]) {
             ++b;
             continue;
@@ -2075,171 +2167,184 @@ static int sub_sort(dsort_ctx *ctx, T *src, T *d_keys, uint64_t n, const uint64_
         int e = b;
         while (e < B && pure[e]) ++e;
         if (hb[e] > hb[b])
-            DSORT_HIP(ctx, hipMemcpyAsync(d_keys + hb[b], src + hb[b], (hb[e] - hb[b]) * sizeof(T),
+            DSORT_HIP(ctx, hipMemcpyAsync(a.d_keys + hb[b], a.src + hb[b], (hb[e] - hb[b]) * sizeof(T),
                                           hipMemcpyDeviceToDevice, s));
         b = e;
     }
     // 1. splitters of every bucket from a regular sample.  A bucket's samples fit one int64 tile,
     // so the tile sort alone sorts them, one workgroup per bucket.
-    if (nsmp) {
-        hipLaunchKernelGGL(sb_sample_kernel<T>, dim3((unsigned)B), dim3(SB_T), 0, s, src, dbi, dch, smp, cmp);
+    if (p.nsmp) {
+        const uint32_t nst = (uint32_t)p.stl.size();
+        hipLaunchKernelGGL(sb_sample_kernel<T>, dim3((unsigned)B), dim3(SB_T), 0, s, a.src, A.bi, A.ch, A.smp, A.cmp);
         DSORT_HIP(ctx, hipGetLastError());
-        const uint4 *stl4 = reinterpret_cast<const uint4 *>(stl);
-        const uint32_t *pnst = reinterpret_cast<const uint32_t *>(stl + B);
+        const uint4 *stl4 = reinterpret_cast<const uint4 *>(A.stl);
+        const uint32_t *pnst = reinterpret_cast<const uint32_t *>(A.stl + B);
         if constexpr (sizeof(T) == 8) {  // int64: sort the keys, rank them, then the composites
-            rc = tile_sort<int64_t, false>(ctx, smp, srt, nsmp, stl4, pnst, sb::Gather{}, nst, s, false);
+            rc = tile_sort<int64_t, false>(ctx, A.smp, A.srt, p.nsmp, stl4, pnst, sb::Gather{}, nst, s, false);
             if (rc) return rc;
-            hipLaunchKernelGGL(sb_rank_kernel, dim3((unsigned)B), dim3(SB_T), 0, s, smp, srt, dbi, cmp);
+            hipLaunchKernelGGL(sb_rank_kernel, dim3((unsigned)B), dim3(SB_T), 0, s, A.smp, A.srt, A.bi, A.cmp);
         }
-        rc = tile_sort<int64_t, false>(ctx, cmp, cmp, nsmp, stl4, pnst, sb::Gather{}, nst, s, false);
+        rc = tile_sort<int64_t, false>(ctx, A.cmp, A.cmp, p.nsmp, stl4, pnst, sb::Gather{}, nst, s, false);
         if (rc) return rc;
-        hipLaunchKernelGGL(sb_splitter_kernel<T>, dim3((unsigned)B), dim3(SB_MAXS), 0, s, cmp, smp, dbi, dch, os, SS, spl,
-                           rng, sfn, stot);
+        hipLaunchKernelGGL(sb_splitter_kernel<T>, dim3((unsigned)B), dim3(SB_MAXS), 0, s, A.cmp, A.smp, A.bi, A.ch, p.os,
+                           p.SS, A.spl, A.rng, A.sfn, A.stot);
         DSORT_HIP(ctx, hipGetLastError());
-    } else if (stot) {
-        DSORT_HIP(ctx, hipMemsetAsync(stot, 0, (size_t)B * SS * 4, s));
+    } else if (A.stot) {
+        DSORT_HIP(ctx, hipMemsetAsync(A.stot, 0, (size_t)B * p.SS * 4, s));
     }
-    const uint32_t mis = (uint32_t)((reinterpret_cast<uintptr_t>(d_keys) / sizeof(T)) & (ALIGN - 1));
-    uint32_t *hn = reinterpret_cast<uint32_t *>(h + h_num);
-    if (local) {
-        // 2. every chunk partitioned in place (cnt = the prefix tables), sub-bucket starts, tiles
-        if (nch) {
-            if ((rc = stage_event(ctx, s, timed, 13))) return rc;
-            hipLaunchKernelGGL(sb_local_kernel<T>, dim3((unsigned)nch), dim3(SB_LT<T>), 0, s, src, dch, dbi, SS, spl, rng,
-                               sfn, cnt, ctx->bk_hot, stot);
-            DSORT_HIP(ctx, hipGetLastError());
-            if ((rc = stage_event(ctx, s, timed, 14))) return rc;
-        }
-        // (the piece tables inside the scan with many buckets; with few, a kernel of their own)
-#ifndef DSORT_PIECES_SCAN_MINB
-#define DSORT_PIECES_SCAN_MINB 256
-#endif
-        const bool pieces_in_scan = B >= DSORT_PIECES_SCAN_MINB;
-        hipLaunchKernelGGL(sb_scan_kernel<true>, dim3((unsigned)B), dim3(SB_MAXS), 0, s, dbi, SS, cnt, nullptr, TILE, 1,
-                           0u, (uint32_t)(2 * (ALIGN - 1)), tt, num, ovf, num + 1, (uint32_t)tmax,
-                           static_cast<const Chunk *>(dch), pieces_in_scan ? pcs : nullptr, PS, (uint32_t)tcap, stot);
+    return DSORT_OK;
+}
+
+// The local path: 2. every chunk partitioned in place, 3. the tile sort gathers the tiles' pieces.
+// overflow: the tiles do not fit the tables (only when many sub-buckets were split) -- nothing is
+// sorted, and the caller takes the scatter path over the partitioned chunks.
+template <typename T>
+static int sub_local_path(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T> &p, const SubArena<T> &A,
+                          bool &overflow) {
+    using namespace sb;
+    constexpr uint64_t ALIGN = KPC<T>;
+    const int B = a.B, TILE = p.TILE, SS = p.SS;
+    const uint64_t n = a.n, tcap = p.tcap;
+    const uint32_t PS = p.PS;
+    T *src = a.src, *d_keys = a.d_keys;
+    hipStream_t s = a.s;
+    const bool timed = a.timed;
+    uint32_t *num = A.num;
+    int rc;
+    // 2. every chunk partitioned in place (cnt = the prefix tables), sub-bucket starts, tiles
+    if (p.nch) {
+        if ((rc = stage_event(ctx, s, timed, 13))) return rc;
+        hipLaunchKernelGGL(sb_local_kernel<T>, dim3((unsigned)p.nch), dim3(SB_LT<T>), 0, s, src, A.ch, A.bi, SS, A.spl,
+                           A.rng, A.sfn, A.cnt, ctx->bk_hot, A.stot);
         DSORT_HIP(ctx, hipGetLastError());
-        const Gather ga{static_cast<const GTile *>(tt), dch, dbi, cnt, pcs, PS, SS, spl, bspl, B,
-                        (uint32_t)std::max<uint64_t>(tcap, 1)};
-        // (few buckets, round 6: the piece tables' kernel goes out before the tile count is read
-        // back, on a grid for the tile tables' capacity -- its workgroups past the count return at
-        // once -- so the early tile sort can follow it and the host's wait for the count runs under
-        // both: a C3 rank's two waves each idled the GPU ~40 us between the scan and the tile sort)
-#ifndef DSORT_PIECES_EARLY
-#define DSORT_PIECES_EARLY 1
-#endif
-        const bool pieces_early = DSORT_PIECES_EARLY && !pieces_in_scan && pcs && tcap > 0;
-        if (pieces_early) {
-            hipLaunchKernelGGL(sb_pieces_kernel, dim3((unsigned)ceil_div(tcap, 4)), dim3(256), 0, s,
-                               static_cast<const GTile *>(tt), num, static_cast<const Chunk *>(dch), cnt, SS, pcs, PS,
-                               (uint32_t)tcap);
-            DSORT_HIP(ctx, hipGetLastError());
-        }
-        DSORT_HIP(ctx, hipMemcpyAsync(hn, num, 8, hipMemcpyDeviceToHost, s));
-        DSORT_HIP(ctx, hipEventRecord(ctx->sub_ev, s));
-        // The tile sort of the first `early` tiles goes out behind the count's read-back, before the
-        // host waits for it: every tile holds at most TILE keys, so there are at least (keys in
-        // tiles) / TILE of them.  The rest follow the count (at 2^30 int32 ~15 % of the tiles), and
-        // the wait -- the read-back, then the launch -- runs under the first part instead of idling
-        // the GPU (about 35 us per sort).  (With the piece tables made by the scan, or by their own
-        // kernel on a grid for the tables' capacity, pieces_early.  Not under a stage-1 kill point, which must see
-        // the second level finished and nothing after it.)
-#ifndef DSORT_TILE_EARLY
-#define DSORT_TILE_EARLY 1
-#endif
-        const uint64_t ebound = (n - npure) / (uint64_t)TILE;
-        const uint32_t early = DSORT_TILE_EARLY && (pieces_in_scan || pieces_early) && ctx->opt.kill_after_pass != 1
-                                   ? (uint32_t)std::min<uint64_t>(ebound, tcap)
-                                   : 0u;
-        if (early) {
-            if ((rc = tile_sort_event(ctx, s, timed, 0))) return rc;
-            rc = with_tile_waves<T>(ctx, TILE, [&](auto w) {
-                return tile_sort_begin<T, true, decltype(w)::value>(ctx, src, d_keys, n, nullptr, num, ga, early,
-                                                                    (uint32_t)tcap, s);
-            });
-            if (rc) return rc;
-        }
-        // (the tile count sizes the grid: a grid at its bound, 9x the tiles at 2^30 int32, cost
-        // more in empty workgroups than this wait -- measured 10.6 vs 10.1 ms)
-        if (int rc_ = sync_event(ctx, ctx->sub_ev, "tile count")) return rc_;
-        const uint32_t ntiles = hn[0], novf = hn[1];
-        // Beyond the tile tables (only when many sub-buckets were split): the scatter path over the
-        // partitioned chunks -- its sample takes single keys, since a run of adjacent keys now lies
-        // in one sub-bucket of this attempt.
-        if (ntiles > tmax || ntiles > tcap) {
-            // (the early tile sort still reads the tables the scatter path's side-stream uploads
-            // overwrite: it finishes first -- its output is rewritten by that path)
-            if (early)
-                if (int rc_ = sync_stream(ctx, s, "early tile sort")) return rc_;
-            ctx->stats.sub_scatter_fallback = 1;
-            // (fill_keys passed on: the retry fills the dropped pure buckets itself instead of relying
-            // on this attempt's queued fill -- ADVICE r5)
-            return sub_sort<T>(ctx, src, d_keys, n, hb, B, m, s, timed, false, pure, pure_done, bspl, true, pm,
-                               fill_keys);
-        }
-        // every tile's piece table
-        if (ntiles && !pieces_in_scan && !pieces_early) {
-            hipLaunchKernelGGL(sb_pieces_kernel, dim3((unsigned)ceil_div(ntiles, 4)), dim3(256), 0, s,
-                               static_cast<const GTile *>(tt), num, static_cast<const Chunk *>(dch), cnt, SS, pcs, PS,
-                               (uint32_t)tcap);
-            DSORT_HIP(ctx, hipGetLastError());
-        }
-        fault_point(ctx, s, 1);  // second-level partition done
-        ctx->stats.merge_passes = 0;
-        // 3. tile sort: gathered from the chunks into d_keys
-        if (early) {  // (ntiles >= early)
-            rc = with_tile_waves<T>(ctx, TILE, [&](auto w) {
-                constexpr int W = decltype(w)::value;
-                int r = tile_sort_more<T, true, W>(ctx, src, d_keys, n, nullptr, num, ga, early,
-                                                   ntiles > early ? ntiles - early : 0u, (uint32_t)tcap, s);
-                return r ? r : tile_sort_end<T, true, W>(ctx, src, d_keys, n, nullptr, num, ga, ntiles, (uint32_t)tcap, s);
-            });
-            if (rc) return rc;
-            if ((rc = tile_sort_event(ctx, s, timed, 1))) return rc;
-        } else if (ntiles) {
-            rc = tile_sort<T, true>(ctx, src, d_keys, n, nullptr, num, ga, ntiles, s, timed, TILE);
-            if (rc) return rc;
-        }
-        if ((rc = stage_event(ctx, s, timed, 1))) return rc;
-        fault_point(ctx, s, 2);  // tile sort done (a split sub-bucket's merge follows)
-        // sub-buckets above a tile (a sampling outlier): their split tiles' outputs merged (src,
-        // read by the tile sort, is free scratch now)
-        if (novf) {
-            rc = merge_split_subbuckets<T>(ctx, ovf, novf, static_cast<const GTile *>(tt), d_keys, s);
-            if (rc) return rc;
-        }
-        if (timed && ctx->ev_ok) {
-            DSORT_HIP(ctx, hipEventRecord(ctx->ev[ctx->ev_done], s));
-            ctx->ev_mask |= 1u << ctx->ev_done;
-        }
+        if ((rc = stage_event(ctx, s, timed, 14))) return rc;
+    }
+    // (the piece tables inside the scan with many buckets; with few, a kernel of their own)
+    constexpr int PIECES_SCAN_MINB = 256;
+    const bool pieces_in_scan = B >= PIECES_SCAN_MINB;
+    hipLaunchKernelGGL(sb_scan_kernel<true>, dim3((unsigned)B), dim3(SB_MAXS), 0, s, A.bi, SS, A.cnt, nullptr, TILE, 1,
+                       0u, (uint32_t)(2 * (ALIGN - 1)), A.tt, num, A.ovf, num + 1, (uint32_t)p.tmax,
+                       static_cast<const Chunk *>(A.ch), pieces_in_scan ? A.pcs : nullptr, PS, (uint32_t)tcap, A.stot);
+    DSORT_HIP(ctx, hipGetLastError());
+    const GTile *gtiles = static_cast<const GTile *>(A.tt);
+    const Gather ga{gtiles, A.ch, A.bi, A.cnt, A.pcs, PS, SS, A.spl, a.bspl, B, (uint32_t)std::max<uint64_t>(tcap, 1)};
+    // (few buckets, round 6: the piece tables' kernel goes out before the tile count is read
+    // back, on a grid for the tile tables' capacity -- its workgroups past the count return at
+    // once -- so the early tile sort can follow it and the host's wait for the count runs under
+    // both: a C3 rank's two waves each idled the GPU ~40 us between the scan and the tile sort)
+    const bool pieces_early = !pieces_in_scan && A.pcs && tcap > 0;
+    if (pieces_early) {
+        hipLaunchKernelGGL(sb_pieces_kernel, dim3((unsigned)ceil_div(tcap, 4)), dim3(256), 0, s, gtiles, num,
+                           static_cast<const Chunk *>(A.ch), A.cnt, SS, A.pcs, PS, (uint32_t)tcap);
+        DSORT_HIP(ctx, hipGetLastError());
+    }
+    DSORT_HIP(ctx, hipMemcpyAsync(A.hn, num, 8, hipMemcpyDeviceToHost, s));
+    DSORT_HIP(ctx, hipEventRecord(ctx->sub_ev, s));
+    // The tile sort of the first `early` tiles goes out behind the count's read-back, before the
+    // host waits for it: every tile holds at most TILE keys, so there are at least (keys in
+    // tiles) / TILE of them.  The rest follow the count (at 2^30 int32 ~15 % of the tiles), and
+    // the wait -- the read-back, then the launch -- runs under the first part instead of idling
+    // the GPU (about 35 us per sort).  (With the piece tables made by the scan, or by their own
+    // kernel on a grid for the tables' capacity, pieces_early.  Not under a stage-1 kill point, which must see
+    // the second level finished and nothing after it.)
+    const uint64_t ebound = (n - p.npure) / (uint64_t)TILE;
+    const uint32_t early = (pieces_in_scan || pieces_early) && ctx->opt.kill_after_pass != 1
+                               ? (uint32_t)std::min<uint64_t>(ebound, tcap)
+                               : 0u;
+    if (early) {
+        if ((rc = tile_sort_event(ctx, s, timed, 0))) return rc;
+        rc = with_tile_waves<T>(ctx, TILE, [&](auto w) {
+            return tile_sort_begin<T, true, decltype(w)::value>(ctx, src, d_keys, n, nullptr, num, ga, early,
+                                                                (uint32_t)tcap, s);
+        });
+        if (rc) return rc;
+    }
+    // (the tile count sizes the grid: a grid at its bound, 9x the tiles at 2^30 int32, cost
+    // more in empty workgroups than this wait -- measured 10.6 vs 10.1 ms)
+    if (int rc_ = sync_event(ctx, ctx->sub_ev, "tile count")) return rc_;
+    const uint32_t ntiles = A.hn[0], novf = A.hn[1];
+    if (ntiles > p.tmax || ntiles > tcap) {
+        // (the early tile sort still reads the tables the scatter path's side-stream uploads
+        // overwrite: it finishes first -- its output is rewritten by that path)
+        if (early)
+            if (int rc_ = sync_stream(ctx, s, "early tile sort")) return rc_;
+        ctx->stats.sub_scatter_fallback = 1;
+        overflow = true;
         return DSORT_OK;
     }
+    // every tile's piece table
+    if (ntiles && !pieces_in_scan && !pieces_early) {
+        hipLaunchKernelGGL(sb_pieces_kernel, dim3((unsigned)ceil_div(ntiles, 4)), dim3(256), 0, s, gtiles, num,
+                           static_cast<const Chunk *>(A.ch), A.cnt, SS, A.pcs, PS, (uint32_t)tcap);
+        DSORT_HIP(ctx, hipGetLastError());
+    }
+    fault_point(ctx, s, 1);  // second-level partition done
+    ctx->stats.merge_passes = 0;
+    // 3. tile sort: gathered from the chunks into d_keys
+    if (early) {  // (ntiles >= early)
+        rc = with_tile_waves<T>(ctx, TILE, [&](auto w) {
+            constexpr int W = decltype(w)::value;
+            int r = tile_sort_more<T, true, W>(ctx, src, d_keys, n, nullptr, num, ga, early,
+                                               ntiles > early ? ntiles - early : 0u, (uint32_t)tcap, s);
+            return r ? r : tile_sort_end<T, true, W>(ctx, src, d_keys, n, nullptr, num, ga, ntiles, (uint32_t)tcap, s);
+        });
+        if (rc) return rc;
+        if ((rc = tile_sort_event(ctx, s, timed, 1))) return rc;
+    } else if (ntiles) {
+        rc = tile_sort<T, true>(ctx, src, d_keys, n, nullptr, num, ga, ntiles, s, timed, TILE);
+        if (rc) return rc;
+    }
+    if ((rc = stage_event(ctx, s, timed, 1))) return rc;
+    fault_point(ctx, s, 2);  // tile sort done (a split sub-bucket's merge follows)
+    // sub-buckets above a tile (a sampling outlier): their split tiles' outputs merged (src,
+    // read by the tile sort, is free scratch now)
+    if (novf) {
+        rc = merge_split_subbuckets<T>(ctx, A.ovf, novf, gtiles, d_keys, s);
+        if (rc) return rc;
+    }
+    return sort_done_event(ctx, s, timed);
+}
+
+// The scatter path: 2. histograms, sub-bucket starts, tiles; 3. every key scattered to its
+// sub-bucket in d_keys and tile-sorted in place; 4. the oversized sub-buckets' merges.
+template <typename T>
+static int sub_scatter_path(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T> &p, const SubArena<T> &A) {
+    using namespace sb;
+    constexpr uint64_t ALIGN = KPC<T>;
+    const int B = a.B, TILE = p.TILE, SS = p.SS;
+    const uint64_t nch = p.nch;
+    T *src = a.src, *d_keys = a.d_keys;
+    hipStream_t s = a.s;
+    const bool timed = a.timed;
+    uint32_t *num = A.num;
+    const uint32_t mis = (uint32_t)((reinterpret_cast<uintptr_t>(d_keys) / sizeof(T)) & (ALIGN - 1));
+    int rc;
     // 2. histograms, sub-bucket starts, tiles
     if (nch) {
         if ((rc = stage_event(ctx, s, timed, 13))) return rc;
-        hipLaunchKernelGGL(sb_hist_kernel<T>, dim3((unsigned)nch), dim3(SB_T), 0, s, src, dch, dbi, SS, spl, rng,
-                           sfn, cnt);
+        hipLaunchKernelGGL(sb_hist_kernel<T>, dim3((unsigned)nch), dim3(SB_T), 0, s, src, A.ch, A.bi, SS, A.spl, A.rng,
+                           A.sfn, A.cnt);
         DSORT_HIP(ctx, hipGetLastError());
     }
-    hipLaunchKernelGGL(sb_scan_kernel<false>, dim3((unsigned)B), dim3(SB_MAXS), 0, s, dbi, SS, cnt, offs, TILE,
-                       (int)ALIGN, mis, 0u, tt, num, ovf, num + 1, (uint32_t)tmax, nullptr, nullptr, 0u, 0u, nullptr);
+    hipLaunchKernelGGL(sb_scan_kernel<false>, dim3((unsigned)B), dim3(SB_MAXS), 0, s, A.bi, SS, A.cnt, A.offs, TILE,
+                       (int)ALIGN, mis, 0u, A.tt, num, A.ovf, num + 1, (uint32_t)p.tmax, nullptr, nullptr, 0u, 0u, nullptr);
     DSORT_HIP(ctx, hipGetLastError());
-    DSORT_HIP(ctx, hipMemcpyAsync(hn, num, 8, hipMemcpyDeviceToHost, s));
+    DSORT_HIP(ctx, hipMemcpyAsync(A.hn, num, 8, hipMemcpyDeviceToHost, s));
     DSORT_HIP(ctx, hipEventRecord(ctx->sub_ev, s));
     // 3. scatter into d_keys (the host reads the tile count meanwhile), tile sort in place
     if (nch) {
-        hipLaunchKernelGGL(sb_scatter_kernel<T>, dim3((unsigned)nch), dim3(SB_T), 0, s, src, d_keys, dch,
-                           (uint32_t)nch, dbi, SS, spl, rng, sfn, offs);
+        hipLaunchKernelGGL(sb_scatter_kernel<T>, dim3((unsigned)nch), dim3(SB_T), 0, s, src, d_keys, A.ch,
+                           (uint32_t)nch, A.bi, SS, A.spl, A.rng, A.sfn, A.offs);
         DSORT_HIP(ctx, hipGetLastError());
         if ((rc = stage_event(ctx, s, timed, 14))) return rc;
     }
     if (int rc_ = sync_event(ctx, ctx->sub_ev, "tile count")) return rc_;
-    const uint32_t ntiles = hn[0], novf = hn[1];
-    if (ntiles > tmax || novf > nsubs) return set_err(ctx, DSORT_EHIP, "sub-bucket packing overflow");
+    const uint32_t ntiles = A.hn[0], novf = A.hn[1];
+    if (ntiles > p.tmax || novf > p.nsubs) return set_err(ctx, DSORT_EHIP, "sub-bucket packing overflow");
     fault_point(ctx, s, 1);  // second-level partition done
     ctx->stats.merge_passes = 0;
     if (ntiles) {
-        rc = tile_sort<T, false>(ctx, d_keys, d_keys, n, static_cast<const uint4 *>(tt), num, Gather{}, ntiles, s,
+        rc = tile_sort<T, false>(ctx, d_keys, d_keys, a.n, static_cast<const uint4 *>(A.tt), num, Gather{}, ntiles, s,
                                  timed, TILE);
         if (rc) return rc;
     }
@@ -2254,7 +2359,7 @@ static int sub_sort(dsort_ctx *ctx, T *src, T *d_keys, uint64_t n, const uint64_
     //    still sending -- as merge_split_subbuckets does on the local path.)
     if (novf) {
         std::vector<Ovf> ov(novf);
-        DSORT_HIP(ctx, hipMemcpyAsync(ov.data(), ovf, novf * sizeof(Ovf), hipMemcpyDeviceToHost, s));
+        DSORT_HIP(ctx, hipMemcpyAsync(ov.data(), A.ovf, novf * sizeof(Ovf), hipMemcpyDeviceToHost, s));
         if (int rc_ = sync_stream(ctx, s, "sort stream")) return rc_;
         uint64_t mx = 0;
         for (const Ovf &o : ov) mx = o.len > mx ? o.len : mx;
@@ -2276,11 +2381,37 @@ static int sub_sort(dsort_ctx *ctx, T *src, T *d_keys, uint64_t n, const uint64_
         ctx->stats.merge_passes = lv;
         ctx->stats.sub_split_subbuckets = (int)novf;
     }
-    if (timed && ctx->ev_ok) {
-        DSORT_HIP(ctx, hipEventRecord(ctx->ev[ctx->ev_done], s));
-        ctx->ev_mask |= 1u << ctx->ev_done;
+    return sort_done_event(ctx, s, timed);
+}
+
+// The second level: plan, stage, pure buckets and splitters, then one of the two paths.
+template <typename T>
+static int sub_sort(dsort_ctx *ctx, T *src, T *d_keys, uint64_t n, const uint64_t *hb, int B, uint64_t m_in,
+                    hipStream_t s, bool timed, bool local, const uint8_t *pure, bool pure_done, const void *bspl,
+                    const PieceMap<T> *pm = nullptr, const T *fill_keys = nullptr) {
+    const SubArgs<T> a{src, d_keys, n, hb, B, s, timed, pure, pure_done, bspl, pm, fill_keys};
+    SubPlan<T> p;
+    SubArena<T> A;
+    const auto prepare = [&](uint64_t m, bool loc, bool retry) -> int {
+        p = sub_plan<T>(ctx->opt, a, m, loc, retry);
+        ctx->stats.tile_keys = p.TILE;
+        if (p.fell_back) ctx->stats.sub_scatter_fallback = 1;
+        if (int rc = sub_stage<T>(ctx, a, p, A)) return rc;
+        return sub_splitters<T>(ctx, a, p, A);
+    };
+    int rc = prepare(m_in, local, false);
+    if (rc) return rc;
+    if (p.local) {
+        bool overflow = false;
+        rc = sub_local_path<T>(ctx, a, p, A, overflow);
+        if (rc || !overflow) return rc;
+        // Beyond the tile tables: the scatter path over the partitioned chunks -- its sample takes
+        // single keys (retry), since a run of adjacent keys now lies in one sub-bucket of this
+        // attempt.  (It fills the dropped pure buckets itself instead of relying on this attempt's
+        // queued fill -- ADVICE r5.)
+        if ((rc = prepare(p.m, false, true))) return rc;
     }
-    return DSORT_OK;
+    return sub_scatter_path<T>(ctx, a, p, A);
 }
 
 // The first level's device arena (ctx->bucket): the splitter samples (their layout is the
@@ -2298,7 +2429,7 @@ struct BkLayout {
     uint64_t *cst;  // the bucket exchange's compacted starts (pure buckets of size 0, bucket_scan_kernel)
     bk::TileRef *tt;
     bk::BkMap *map;
-    uint32_t *ids;  // every key's bucket (bk::BkIds: 2 or 3 per word), else null
+    uint32_t *ids;  // every key's bucket (bk::BkIds: 3 per word), else null
 };
 template <typename T>
 static int bk_layout(dsort_ctx *ctx, uint64_t n, int B, size_t smp_bytes, BkLayout<T> &L) {
@@ -2368,27 +2499,17 @@ static int first_level(dsort_ctx *ctx, const T *d_in, uint64_t n, uint64_t ioff,
     // empty workgroups, about 40 us)
     // int64 (round 5): likewise which scatter variant -- with or without the histogram's bucket ids
     // (launching both and letting the other return cost its grid of ~11 K workgroups, 48 us at C4)
-#ifndef DSORT_IDS_READBACK
-#define DSORT_IDS_READBACK 1
-#endif
-    constexpr bool RB = !Comp<T>::ADAPT || (BkIds<T>::ON && DSORT_IDS_READBACK);
-    bool ad = false, ids = false;
     BkMap *hm = reinterpret_cast<BkMap *>(reinterpret_cast<char *>(hb) + (size_t)(BK_MAXB + 1) * 8 + (size_t)BK_MAXB * 16);
-    if constexpr (RB) {
-        DSORT_HIP(ctx, hipMemcpyAsync(hm, L.map, sizeof(BkMap), hipMemcpyDeviceToHost, s));
-        DSORT_HIP(ctx, hipEventRecord(ctx->bucket_ev, s));
-    }
+    DSORT_HIP(ctx, hipMemcpyAsync(hm, L.map, sizeof(BkMap), hipMemcpyDeviceToHost, s));
+    DSORT_HIP(ctx, hipEventRecord(ctx->bucket_ev, s));
     if ((rc = stage_event(ctx, s, timed, 9))) return rc;
     // (int32: the fixed map's histogram goes first -- it returns at once when the map is adaptive
     // -- so the GPU is busy while the host reads the map's choice; only the adaptive case launches
     // a second instance behind it)
     hipLaunchKernelGGL((bucket_hist_kernel<T, false>), dim3((unsigned)L.G), dim3(BK_T), 0, s, d_in, n, L.spl, L.map, B,
                        BP, L.subs, L.cnt, ioff, L.ids);
-    if constexpr (RB) {
-        if (int rc_ = sync_event(ctx, ctx->bucket_ev, "slot map")) return rc_;
-        ad = !Comp<T>::ADAPT && hm->ad != 0;
-        ids = BkIds<T>::ON && hm->ids != 0;
-    }
+    if (int rc_ = sync_event(ctx, ctx->bucket_ev, "slot map")) return rc_;
+    const bool ad = !Comp<T>::ADAPT && hm->ad != 0, ids = BkIds<T>::ON && hm->ids != 0;
     if constexpr (!Comp<T>::ADAPT) {
         if (ad)
             hipLaunchKernelGGL((bucket_hist_kernel<T, true>), dim3((unsigned)L.G), dim3(BK_T), 0, s, d_in, n, L.spl,
@@ -2415,30 +2536,23 @@ static int first_level(dsort_ctx *ctx, const T *d_in, uint64_t n, uint64_t ioff,
     DSORT_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ready_ev, 0));
     DSORT_HIP(ctx, hipMemcpyAsync(hb, L.bst, (size_t)(B + 1) * 8, hipMemcpyDeviceToHost, ctx->side));
     if (B > 1) DSORT_HIP(ctx, hipMemcpyAsync(hspl, L.spl, (size_t)(B - 1) * sizeof(C), hipMemcpyDeviceToHost, ctx->side));
-    if constexpr (!RB)  // (int64: the map only for the statistics)
-        DSORT_HIP(ctx, hipMemcpyAsync(hm, L.map, sizeof(BkMap), hipMemcpyDeviceToHost, ctx->side));
     DSORT_HIP(ctx, hipEventRecord(ctx->bucket_ev, ctx->side));
     if ((rc = stage_event(ctx, s, timed, 11))) return rc;
-#ifdef DSORT_IDS_ONLY
-    if constexpr (!BkIds<T>::ON)
-#endif
-    {
-        if constexpr (!Comp<T>::ADAPT) {
-            if (ad)
-                hipLaunchKernelGGL((bucket_scatter_lines_kernel<T, false, true>), dim3((unsigned)L.G), dim3(BK_T), 0, s,
-                                   d_in, n, L.spl, L.map, B, BP, L.subs, L.offs, part_out, direct, ioff, L.ids);
-        }
-        if (!ad && !(RB && ids)) {
-            if (!Comp<T>::ADAPT && RB && hm->hot)  // (int32 read the map back: runs of one bucket)
-                hipLaunchKernelGGL((bucket_scatter_lines_kernel<T, false, false, true>), dim3((unsigned)L.G), dim3(BK_T), 0,
-                                   s, d_in, n, L.spl, L.map, B, BP, L.subs, L.offs, part_out, direct, ioff, L.ids);
-            else
-                hipLaunchKernelGGL((bucket_scatter_lines_kernel<T, false, false>), dim3((unsigned)L.G), dim3(BK_T), 0, s,
-                                   d_in, n, L.spl, L.map, B, BP, L.subs, L.offs, part_out, direct, ioff, L.ids);
-        }
+    if constexpr (!Comp<T>::ADAPT) {
+        if (ad)
+            hipLaunchKernelGGL((bucket_scatter_lines_kernel<T, false, true>), dim3((unsigned)L.G), dim3(BK_T), 0, s,
+                               d_in, n, L.spl, L.map, B, BP, L.subs, L.offs, part_out, direct, ioff, L.ids);
     }
-    if constexpr (BkIds<T>::ON)  // (without the read-back: the variant the slot map did not choose returns at once)
-        if (!RB || ids)
+    if (!ad && !ids) {
+        if (!Comp<T>::ADAPT && hm->hot)  // (int32: runs of one bucket)
+            hipLaunchKernelGGL((bucket_scatter_lines_kernel<T, false, false, true>), dim3((unsigned)L.G), dim3(BK_T), 0,
+                               s, d_in, n, L.spl, L.map, B, BP, L.subs, L.offs, part_out, direct, ioff, L.ids);
+        else
+            hipLaunchKernelGGL((bucket_scatter_lines_kernel<T, false, false>), dim3((unsigned)L.G), dim3(BK_T), 0, s,
+                               d_in, n, L.spl, L.map, B, BP, L.subs, L.offs, part_out, direct, ioff, L.ids);
+    }
+    if constexpr (BkIds<T>::ON)
+        if (ids)
             hipLaunchKernelGGL((bucket_scatter_lines_kernel<T, true>), dim3((unsigned)L.G), dim3(BK_T), 0, s, d_in, n,
                                L.spl, L.map, B, BP, L.subs, L.offs, part_out, direct, ioff, L.ids);
     DSORT_HIP(ctx, hipGetLastError());
@@ -2446,7 +2560,7 @@ static int first_level(dsort_ctx *ctx, const T *d_in, uint64_t n, uint64_t ioff,
     fault_point(ctx, s, 0);  // first-level partition done
     if (int rc_ = sync_event(ctx, ctx->bucket_ev, "bucket starts")) return rc_;
     if (hb[B] != n) return set_err(ctx, DSORT_EHIP, "bucket partition lost keys");
-    ctx->stats.first_level_map = !Comp<T>::ADAPT && !ad ? (RB && hm->r2s ? 3 : 0) : hm->mode == 0 ? 1 : 2;
+    ctx->stats.first_level_map = !Comp<T>::ADAPT && !ad ? (hm->r2s ? 3 : 0) : hm->mode == 0 ? 1 : 2;
     return DSORT_OK;
 }
 
@@ -2533,13 +2647,13 @@ static int bucket_sort(dsort_ctx *ctx, const T *d_in, T *d_keys, size_t n, hipSt
         // (the scatter dropped the pure buckets' keys when it had `direct`: the second level fills
         // their output ranges with their key, dsort_bucket.h)
         std::vector<T> fk;
-        if (direct && DSORT_DROP_PURE) {
+        if (direct) {
             fk.assign((size_t)B, T(0));
             for (int b = 1; b + 1 < B; ++b)
                 if (pure[b]) fk[b] = Comp<T>::key_of(hspl[b]);
         }
         return sub_sort<T>(ctx, part_out, d_keys, n, hb, B, m, s, timed, ctx->opt.sub_gather != 0, pure.data(),
-                           direct != nullptr, spl, false, nullptr, fk.empty() ? nullptr : fk.data());
+                           direct != nullptr, spl, nullptr, fk.empty() ? nullptr : fk.data());
     }
     // pass plan: the runs of every bucket; the largest bucket's run count R sets the merge
     // levels L = ceil(log2 R), split into the fewest passes of <= max_logf levels (larger passes
@@ -2788,9 +2902,6 @@ int bx_sample(dsort_ctx *ctx, const T *d_in, const BxPlan &pl, BxSample *d_smp, 
     return DSORT_OK;
 }
 
-#ifndef DSORT_BX_DROP_PURE
-#define DSORT_BX_DROP_PURE 1
-#endif
 template <typename T>
 int bx_partition(dsort_ctx *ctx, const T *d_in, const BxPlan &pl, const BxSample *d_all, hipStream_t s, bool timed,
                  const uint64_t **hb_out, T **part, std::vector<uint8_t> &pure) {
@@ -2832,7 +2943,7 @@ int bx_partition(dsort_ctx *ctx, const T *d_in, const BxPlan &pl, const BxSample
     C *hspl;
     if (pl.n_local) {
         rc = first_level<T>(ctx, d_in, pl.n_local, pl.ioff[pl.me], scratch, nullptr, L, 0u, s, timed, hb, hspl,
-                            DSORT_BX_DROP_PURE != 0);
+                            true);
         if (rc) return rc;
     } else {
         // no keys here: empty buckets (the splitters still go to the host for the second level)
@@ -2847,7 +2958,7 @@ int bx_partition(dsort_ctx *ctx, const T *d_in, const BxPlan &pl, const BxSample
     // (the scatter's rule, bucket_scatter_lines_kernel / bucket_scan_kernel: the same splitters on
     // every rank, which derive every rank's compacted starts from its bucket starts)
     pure.assign((size_t)pl.Btot, 0);
-    for (int g = 1; DSORT_BX_DROP_PURE && g + 1 < pl.Btot; ++g)
+    for (int g = 1; g + 1 < pl.Btot; ++g)
         pure[(size_t)g] = bk::Comp<T>::key_of(hspl[g - 1]) == bk::Comp<T>::key_of(hspl[g]) ? 1 : 0;
     *hb_out = hb;
     *part = scratch;
@@ -2907,7 +3018,7 @@ int bx_local_sort(dsort_ctx *ctx, T *recv, T *out, const BxPlan &pl, const uint6
         ctx->ev_off = last ? 0 : 15;
         ctx->ev_done = last ? 4 : 16;
         rc = sub_sort<T>(ctx, recv, out + out_off, nrecv, hbo.data(), Bl, sub_keys<T>(ctx), s, timed,
-                         ctx->opt.sub_gather != 0, pure.data(), false, L.spl + g0, false, &pm);
+                         ctx->opt.sub_gather != 0, pure.data(), false, L.spl + g0, &pm);
         ctx->ev_done = saved_done;
         ctx->ev_off = saved_off;
         if (w & 1) {
