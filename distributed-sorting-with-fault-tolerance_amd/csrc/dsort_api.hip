@@ -396,7 +396,8 @@ int dsort_finalize(dsort_ctx *ctx) {
                     ctx->local, ctx->recv, ctx->recv2, ctx->small, ctx->text_status,
                     ctx->bucket, ctx->sub, ctx->sub_alt, ctx->stmp, ctx->bxs, ctx->tfb, ctx->fence, ctx->pairs,
                     ctx->spairs_k, ctx->spairs_v, ctx->gat_req, ctx->gat_rreq, ctx->gat_rep, ctx->gat_back,
-                    ctx->gat_small, ctx->a64_b, ctx->a64_idx, ctx->a64_part};
+                    ctx->gat_small, ctx->a64_b, ctx->a64_idx, ctx->a64_part, ctx->s64_k, ctx->s64_i,
+                    ctx->s64_sa, ctx->s64_pos, ctx->s64_got};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->red_host) (void)hipHostFree(ctx->red_host);
@@ -423,6 +424,8 @@ int dsort_finalize(dsort_ctx *ctx) {
     for (auto &e : ctx->pairs_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : ctx->a64_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : ctx->s64_ev)
         if (e) (void)hipEventDestroy(e);
     if (ctx->a64_mm_ev) (void)hipEventDestroy(ctx->a64_mm_ev);
     for (auto &e : ctx->ev)
@@ -505,6 +508,10 @@ int dsort_set_option(dsort_ctx *ctx, int option, int64_t v) {
             if (v != 0 && v != 1) return set_err(ctx, DSORT_EINVAL, "DSORT_OPT_ARGSORT_WIDE: 0 or 1");
             o.argsort_wide = v;
             return DSORT_OK;
+        case DSORT_OPT_TEST_FAIL_LEG:
+            if (v < -1) return set_err(ctx, DSORT_EINVAL, "DSORT_OPT_TEST_FAIL_LEG: -1 or a leg index");
+            o.test_fail_leg = v;
+            return DSORT_OK;
         default:
             return set_err(ctx, DSORT_EINVAL, "unknown option " + std::to_string(option));
     }
@@ -530,6 +537,7 @@ int dsort_get_option(const dsort_ctx *ctx, int option, int64_t *v) {
         case DSORT_OPT_SUB_OVERSAMPLE: *v = o.sub_os; return DSORT_OK;
         case DSORT_OPT_SUB_GATHER: *v = o.sub_gather; return DSORT_OK;
         case DSORT_OPT_ARGSORT_WIDE: *v = o.argsort_wide; return DSORT_OK;
+        case DSORT_OPT_TEST_FAIL_LEG: *v = o.test_fail_leg; return DSORT_OK;
         default: return DSORT_EINVAL;
     }
 }

@@ -44,6 +44,7 @@ struct ExchCall {
     TxSeq seq;
     ExchCall(dsort_ctx *ctx, void *stream, int ncoll);
     void finished() { guard.finished = true; }
+    void failed(int code) { guard.code = code; }  // what the guard reports instead of DSORT_ECOMM
 
   private:
     struct TxScope {
@@ -52,6 +53,13 @@ struct ExchCall {
     } scope;        // (destroyed after the guard: its report still sees the sequence's deadline)
     TxGuard guard;
 };
+
+// A call made of several exchange calls one after the other (the int64 sample argsort's legs) that
+// fails locally BETWEEN two of them -- an arena, a kernel launch -- must not leave its peers blocked
+// in the next one: the failing rank opens that next call, of one collective, and leaves it
+// unfinished, so that its guard reports `code` at the peers' first gate there.  Returns `code`, the
+// context's error message untouched.  (RCCL has no gates: the deadline and the abort flag.)
+int exch_leave(dsort_ctx *ctx, void *stream, int code);
 
 // Every wait of an exchange (stream, RCCL's asynchronous error, abort flag, deadline).
 int exch_wait(dsort_ctx *ctx, hipStream_t s, bool with_stream, double deadline, const char *what,

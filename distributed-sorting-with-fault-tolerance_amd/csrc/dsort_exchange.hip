@@ -51,6 +51,16 @@ ExchCall::ExchCall(dsort_ctx *ctx, void *stream, int ncoll)
     }
 }
 
+int exch_leave(dsort_ctx *ctx, void *stream, int code) {
+    const std::string err = ctx->err;
+    {
+        ExchCall call(ctx, stream, 1);
+        call.failed(code);
+    }  // (the guard's report, at the gate of the collective this rank never runs)
+    ctx->err = err;
+    return code;
+}
+
 // Every wait of an exchange: polls the stream, RCCL's asynchronous error (non-blocking
 // communicator), the abort flag and the deadline, and aborts the communicator on a failure,
 // instead of a hipStreamSynchronize that a dead peer would block forever.

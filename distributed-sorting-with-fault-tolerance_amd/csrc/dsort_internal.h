@@ -69,6 +69,7 @@ struct dsort_opts {
     int64_t sub_os = -1;            // DSORT_OPT_SUB_OVERSAMPLE: -1 = 8 (4 at sub-buckets <= TILE/8)
     int64_t sub_gather = 1;         // DSORT_OPT_SUB_GATHER
     int64_t argsort_wide = 0;       // DSORT_OPT_ARGSORT_WIDE
+    int64_t test_fail_leg = -1;     // DSORT_OPT_TEST_FAIL_LEG
 };
 
 // The context.  One per host thread, bound to one device.
@@ -120,6 +121,22 @@ struct dsort_ctx {
     int a64_legs = 0;             // ... those the last call recorded
     bool a64_ev_ok = false;       // ... all of them
     bool a64_minmax = false;      // the last call ran the reduction (the automatic mode)
+    // the int64 argsort across ranks (dsort_sample_argsort_dev_i64, dsort_pairs64.hip); its packed
+    // words start in `pairs`
+    void *s64_k = nullptr;        // this rank's slice: sorted keys (8 B each) ...
+    size_t s64_k_bytes = 0;
+    void *s64_i = nullptr;        // ... and their global positions (4 B each)
+    size_t s64_i_bytes = 0;
+    void *s64_sa = nullptr;       // wide: the first sort's slice, saved (the second sort reuses recv2)
+    size_t s64_sa_bytes = 0;
+    void *s64_pos = nullptr;      // wide: the low words of a slice, the indices of a gather (4 B each)
+    size_t s64_pos_bytes = 0;
+    void *s64_got = nullptr;      // wide: what a gather brought (8 B per index)
+    size_t s64_got_bytes = 0;
+    static constexpr int kS64Ev = 11;
+    hipEvent_t s64_ev[kS64Ev] = {};  // around its legs (created on first use)
+    int s64_legs = 0;             // ... those the last call recorded
+    bool s64_ev_ok = false;       // ... all of them
     // the distributed gather (dsort_gather.hip): arenas of its own, so that a gather leaves the
     // slices of the preceding sample sort / argsort (recv2, spairs_k, spairs_v) alone
     void *gat_req = nullptr;      // this rank's requests, owner-major (4 B per index)

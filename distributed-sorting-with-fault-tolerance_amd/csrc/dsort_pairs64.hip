@@ -28,12 +28,20 @@
 // HBM bytes per element: min/max reads 8; the narrow pack reads 8 and writes 8, the
 // unpack reads 8 and writes 4 + 8 (keys wanted); the wide pack reads 8 and writes 8, the regroup
 // reads 8 + a random 8 and writes 8, the final kernel reads 8 + a random 8 and writes 4 + 8.
+//
+// Across ranks (dsort_sample_argsort_dev_i64; the algorithm: dsort.h) the same words, with global
+// positions, go through the int64 sample sort, and the wide path's two random reads become
+// distributed gathers (dsort_gather.hip) of the keys and of the first pass's words.  Its kernels
+// stream: the split of a slice into a saved copy and its low words reads 8 and writes 8 + 4 (4
+// without the copy), the regroup reads 8 and writes 8, the final kernel reads 8 + 8 and writes 4 + 8.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
 
 #include <string>
+#include <vector>
 
+#include "dsort_exch.h"
 #include "dsort_internal.h"
 
 namespace dsort {
@@ -137,26 +145,29 @@ __device__ __forceinline__ uint64_t pack_word(uint64_t key, uint64_t i, uint64_t
     return (((key - kmin) << b) | i) ^ SIGN;
 }
 
+// `base` = the global position of keys[0] (a sample argsort; 0 in a local one): element i packs the
+// position base + i.
 template <bool WIDE>
 __global__ void __launch_bounds__(NT) pack64_kernel(const int64_t *__restrict__ keys, uint64_t *__restrict__ packed,
-                                                    uint64_t n, uint64_t kmin, int b) {
+                                                    uint64_t n, uint64_t kmin, int b, uint64_t base) {
     const uint64_t chunks = n >> 8;
     const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
     const uint64_t nwaves = ((uint64_t)gridDim.x * NT) >> 6;
     const uint32_t l = threadIdx.x & 63;
     for (uint64_t c = t >> 6; c < chunks; c += nwaves) {
         const uint64_t e0 = (c << 8) + 2 * l, e1 = e0 + 128;
+        const uint64_t p0 = base + e0, p1 = base + e1;
         const k2_a8 k0 = *reinterpret_cast<const k2_a8 *>(keys + e0);
         const k2_a8 k1 = *reinterpret_cast<const k2_a8 *>(keys + e1);
         __builtin_nontemporal_store(
-            l2{pack_word<WIDE>(k0.x, e0, kmin, b), pack_word<WIDE>(k0.y, e0 + 1, kmin, b)},
+            l2{pack_word<WIDE>(k0.x, p0, kmin, b), pack_word<WIDE>(k0.y, p0 + 1, kmin, b)},
             reinterpret_cast<l2 *>(packed + e0));
         __builtin_nontemporal_store(
-            l2{pack_word<WIDE>(k1.x, e1, kmin, b), pack_word<WIDE>(k1.y, e1 + 1, kmin, b)},
+            l2{pack_word<WIDE>(k1.x, p1, kmin, b), pack_word<WIDE>(k1.y, p1 + 1, kmin, b)},
             reinterpret_cast<l2 *>(packed + e1));
     }
     const uint64_t i = (chunks << 8) + t;  // the n % 256 last elements, one each
-    if (i < n) packed[i] = pack_word<WIDE>((uint64_t)keys[i], i, kmin, b);
+    if (i < n) packed[i] = pack_word<WIDE>((uint64_t)keys[i], base + i, kmin, b);
 }
 
 // ------------------------------------------------------------------ narrow unpack --------
@@ -255,6 +266,93 @@ __global__ void __launch_bounds__(NT) final64_kernel(const uint64_t *__restrict_
     }
 }
 
+// ------------------------------------------------------------------ across ranks ---------
+// The wide path of dsort_sample_argsort_dev_i64 has a distributed gather where the local one reads
+// at random, so its three kernels stream: 16-byte loads of arenas, the shapes as above.
+
+// low[i] = the low word of S[i] (the indices of the gather that follows); copy (NULL: not wanted)
+// = S, which the next sample sort overwrites
+__global__ void __launch_bounds__(NT) split64_kernel(const uint64_t *__restrict__ S, uint64_t *__restrict__ copy,
+                                                     uint32_t *__restrict__ low, uint64_t n) {
+    const uint64_t chunks = n >> 8;
+    const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * NT) >> 6;
+    const uint32_t l = threadIdx.x & 63;
+    for (uint64_t c = t >> 6; c < chunks; c += nwaves) {
+        const uint64_t e0 = (c << 8) + 2 * l, e1 = e0 + 128;
+        const l2 a = *reinterpret_cast<const l2 *>(S + e0);
+        const l2 d = *reinterpret_cast<const l2 *>(S + e1);
+        __builtin_nontemporal_store(u2_a4{(uint32_t)a.x, (uint32_t)a.y}, reinterpret_cast<u2_a4 *>(low + e0));
+        __builtin_nontemporal_store(u2_a4{(uint32_t)d.x, (uint32_t)d.y}, reinterpret_cast<u2_a4 *>(low + e1));
+        if (copy) {
+            __builtin_nontemporal_store(a, reinterpret_cast<l2 *>(copy + e0));
+            __builtin_nontemporal_store(d, reinterpret_cast<l2 *>(copy + e1));
+        }
+    }
+    const uint64_t i = (chunks << 8) + t;
+    if (i < n) {
+        const uint64_t w = S[i];
+        low[i] = (uint32_t)w;
+        if (copy) copy[i] = w;
+    }
+}
+
+// B[j] = hi32(K[j]) : (off + j), K the whole keys in the order of the first pass and off this
+// rank's first rank in that order
+__global__ void __launch_bounds__(NT) regroup_stream64_kernel(const uint64_t *__restrict__ K, uint64_t *__restrict__ B,
+                                                              uint64_t n, uint32_t off) {
+    const uint64_t chunks = n >> 8;
+    const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * NT) >> 6;
+    const uint32_t l = threadIdx.x & 63;
+    for (uint64_t c = t >> 6; c < chunks; c += nwaves) {
+        const uint64_t e0 = (c << 8) + 2 * l, e1 = e0 + 128;
+        const uint32_t j0 = off + (uint32_t)e0, j1 = off + (uint32_t)e1;
+        const l2 a = *reinterpret_cast<const l2 *>(K + e0);
+        const l2 d = *reinterpret_cast<const l2 *>(K + e1);
+        __builtin_nontemporal_store(l2{word((uint32_t)(a.x >> 32), j0), word((uint32_t)(a.y >> 32), j0 + 1)},
+                                    reinterpret_cast<l2 *>(B + e0));
+        __builtin_nontemporal_store(l2{word((uint32_t)(d.x >> 32), j1), word((uint32_t)(d.y >> 32), j1 + 1)},
+                                    reinterpret_cast<l2 *>(B + e1));
+    }
+    const uint64_t i = (chunks << 8) + t;
+    if (i < n) B[i] = word((uint32_t)(K[i] >> 32), off + (uint32_t)i);
+}
+
+// SB[r] = hi32 : j and AW[r] = the first pass's word of rank j, (lo ^ BIAS) : p:
+// idx_out[r] = p, keys_out[r] (NULL: not wanted) = hi32 : lo
+__global__ void __launch_bounds__(NT) final_stream64_kernel(const uint64_t *__restrict__ SB,
+                                                            const uint64_t *__restrict__ AW,
+                                                            int64_t *__restrict__ keys_out,
+                                                            uint32_t *__restrict__ idx_out, uint64_t n) {
+    const uint64_t chunks = n >> 8;
+    const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * NT) >> 6;
+    const uint32_t l = threadIdx.x & 63;
+    auto key_of = [](uint64_t bw, uint64_t aw) { return word((uint32_t)(bw >> 32), (uint32_t)(aw >> 32) ^ BIAS); };
+    for (uint64_t c = t >> 6; c < chunks; c += nwaves) {
+        const uint64_t e0 = (c << 8) + 2 * l, e1 = e0 + 128;
+        const l2 a = *reinterpret_cast<const l2 *>(AW + e0);
+        const l2 d = *reinterpret_cast<const l2 *>(AW + e1);
+        __builtin_nontemporal_store(u2_a4{(uint32_t)a.x, (uint32_t)a.y}, reinterpret_cast<u2_a4 *>(idx_out + e0));
+        __builtin_nontemporal_store(u2_a4{(uint32_t)d.x, (uint32_t)d.y}, reinterpret_cast<u2_a4 *>(idx_out + e1));
+        if (keys_out) {
+            const l2 x = *reinterpret_cast<const l2 *>(SB + e0);
+            const l2 y = *reinterpret_cast<const l2 *>(SB + e1);
+            __builtin_nontemporal_store(k2_a8{key_of(x.x, a.x), key_of(x.y, a.y)},
+                                        reinterpret_cast<k2_a8 *>(keys_out + e0));
+            __builtin_nontemporal_store(k2_a8{key_of(y.x, d.x), key_of(y.y, d.y)},
+                                        reinterpret_cast<k2_a8 *>(keys_out + e1));
+        }
+    }
+    const uint64_t i = (chunks << 8) + t;
+    if (i < n) {
+        const uint64_t aw = AW[i];
+        idx_out[i] = (uint32_t)aw;
+        if (keys_out) keys_out[i] = (int64_t)key_of(SB[i], aw);
+    }
+}
+
 // ------------------------------------------------------------------ host -----------------
 static unsigned grid_for(uint64_t lanes) {
     const uint64_t g = (lanes + NT - 1) / NT;
@@ -348,7 +446,8 @@ static int argsort64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uin
     const unsigned grid = grid_for(((uint64_t)n + 3) / 4);
     int done = 0, src;
     if (passes == 1) {
-        hipLaunchKernelGGL((pack64_kernel<false>), dim3(grid), dim3(NT), 0, s, keys, A, (uint64_t)n, (uint64_t)kmin, b);
+        hipLaunchKernelGGL((pack64_kernel<false>), dim3(grid), dim3(NT), 0, s, keys, A, (uint64_t)n, (uint64_t)kmin, b,
+                           (uint64_t)0);
         DSORT_HIP(ctx, hipGetLastError());
         leg_event(ctx, s);
         // DSORT_ESTAGE (the kill stage was never reached) leaves a valid output: the rest still runs
@@ -362,7 +461,8 @@ static int argsort64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uin
         rc = ensure(ctx, &ctx->a64_b, &ctx->a64_b_bytes, n * 8, "argsort second arena");
         if (rc) return rc;
         uint64_t *B = static_cast<uint64_t *>(ctx->a64_b);
-        hipLaunchKernelGGL((pack64_kernel<true>), dim3(grid), dim3(NT), 0, s, keys, A, (uint64_t)n, (uint64_t)0, 0);
+        hipLaunchKernelGGL((pack64_kernel<true>), dim3(grid), dim3(NT), 0, s, keys, A, (uint64_t)n, (uint64_t)0, 0,
+                           (uint64_t)0);
         DSORT_HIP(ctx, hipGetLastError());
         leg_event(ctx, s);
         src = inner_sort(ctx, A, n, s, &done);
@@ -386,6 +486,286 @@ static int argsort64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uin
                            std::to_string(n) + " int64 keys has " + std::to_string(done) + " stages in " +
                            std::to_string(passes) + " sort(s) (kill points 0.." + std::to_string(done - 1) + ")");
     return src;
+}
+
+// ------------------------------------------------------------------ across ranks: host ---
+// The host rule of the decision (dsort_plan_sample_argsort_i64) and what the call needs besides.
+struct SamplePlan {
+    uint64_t E = 0, total = 0;  // the end of the global range, the keys of all ranks
+    int64_t kmin = 0, kmax = 0;
+    int b = 1, passes = 0;
+};
+static int plan_sample_argsort64(int P, const uint64_t *first, const uint64_t *count, const int64_t *kmin,
+                                 const int64_t *kmax, SamplePlan *out) {
+    std::vector<uint64_t> lo((size_t)P), hi((size_t)P);
+    std::vector<int32_t> own((size_t)P);
+    int nr = 0;
+    if (dsort_plan_gather_table(P, first, count, lo.data(), hi.data(), own.data(), &nr)) return DSORT_EINVAL;
+    SamplePlan p;
+    for (int r = 0; r < P; ++r) {
+        if (!count[r]) continue;
+        if (kmin[r] > kmax[r]) return DSORT_EINVAL;
+        p.kmin = !p.total || kmin[r] < p.kmin ? kmin[r] : p.kmin;
+        p.kmax = !p.total || kmax[r] > p.kmax ? kmax[r] : p.kmax;
+        p.E = first[r] + count[r] > p.E ? first[r] + count[r] : p.E;
+        p.total += count[r];
+    }
+    if (int rc = plan_argsort64(p.E, p.kmin, p.kmax, &p.b, &p.passes)) return rc;
+    *out = p;
+    return DSORT_OK;
+}
+
+static void sample_leg_event(dsort_ctx *ctx, hipStream_t s) {
+    if (!ctx->s64_ev_ok || ctx->s64_legs >= dsort_ctx::kS64Ev) return;
+    hipEvent_t &e = ctx->s64_ev[ctx->s64_legs];
+    ctx->s64_ev_ok = (e || hipEventCreate(&e) == hipSuccess) && hipEventRecord(e, s) == hipSuccess;
+    if (ctx->s64_ev_ok) ++ctx->s64_legs;
+}
+
+static int launched(dsort_ctx *ctx, const char *what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? DSORT_OK : hip_err(ctx, e, what);
+}
+
+// dsort_sample_argsort_dev_i64 behind its argument checks (dsort.h has the algorithm).  The call is
+// a chain of exchange calls, the LEGS: 0 the decision, 1 the first sample sort, and on the wide
+// path 2 the all-gather of the slice lengths, 3 the key gather, 4 the second sample sort, 5 the
+// final gather.  Each takes the comm mutex and runs its gates itself, so nothing here holds either
+// between two of them; what fails there (an arena, a launch) leaves through exch_leave while legs
+// are still ahead, so that the peers meet the failure at their next gate.
+static int sample_argsort64(dsort_ctx *ctx, const int64_t *keys, size_t n, uint64_t first, int64_t **keys_out,
+                            uint32_t **idx_out, size_t *n_out, void *stream) {
+    const hipStream_t s = pick_stream(ctx, stream);
+    bool ahead = true;  // legs ahead: the peers wait at a gate
+    auto fail = [&](int rc) { return ahead ? exch_leave(ctx, stream, rc) : rc; };
+    // DSORT_OPT_TEST_FAIL_LEG: a local failure right before leg k
+    auto before_leg = [&](int k) -> int {
+        if (ctx->opt.test_fail_leg != k) return DSORT_OK;
+        return fail(set_err(ctx, DSORT_EHIP, "injected local failure before leg " + std::to_string(k) +
+                                                 " of the int64 sample argsort (DSORT_OPT_TEST_FAIL_LEG)"));
+    };
+    // The kill options act inside the first inner sample sort only; whatever leaves the call finds
+    // them as the caller set them.
+    struct KeepOpts {
+        dsort_ctx *c;
+        const int64_t stage, exch;
+        ~KeepOpts() {
+            c->opt.kill_after_pass = stage;
+            c->opt.kill_in_exchange = exch;
+        }
+    } keep{ctx, ctx->opt.kill_after_pass, ctx->opt.kill_in_exchange};
+
+    int rc = order_begin(ctx, s);
+    if (rc) return fail(rc);
+    ctx->s64_legs = 0;
+    ctx->s64_ev_ok = ctx->ev_ok && ctx->opt.stage_timing;
+    sample_leg_event(ctx, s);
+
+    // leg 0, the decision: every rank's range, min and max and option, and the host rule on them
+    if ((rc = before_leg(0))) return rc;
+    const bool forced = ctx->opt.argsort_wide != 0;
+    SamplePlan pl;
+    int P = 1;
+    bool never = false;  // the kill stage lies beyond the first sort's stages
+    int stages = 0;
+    {
+        ExchCall call(ctx, stream, 1);
+        if (call.rc) return call.rc;
+        P = call.P;
+        int64_t kmin = 0, kmax = 0;
+        if (n && !forced && (rc = minmax(ctx, keys, n, s, &kmin, &kmax))) return rc;
+        const uint64_t mine[5] = {first, (uint64_t)n, (uint64_t)kmin, (uint64_t)kmax, forced ? 1u : 0u};
+        std::vector<uint64_t> all((size_t)5 * P);
+        rc = allgather_u64(ctx, mine, 5, all.data(), s, call.deadline, "argsort decision all-gather");
+        if (rc) return rc;
+        call.finished();  // (every rank sees the same table: what leaves below leaves on all of them)
+        ahead = false;
+        std::vector<uint64_t> f((size_t)P), c((size_t)P);
+        std::vector<int64_t> lo((size_t)P), hi((size_t)P);
+        for (int r = 0; r < P; ++r) {
+            f[r] = all[5 * r], c[r] = all[5 * r + 1];
+            lo[r] = forced ? 0 : (int64_t)all[5 * r + 2], hi[r] = forced ? 0 : (int64_t)all[5 * r + 3];
+            if (all[5 * r + 4] != all[4])
+                return set_err(ctx, DSORT_EINVAL, "sample argsort: the ranks disagree on DSORT_OPT_ARGSORT_WIDE (rank 0 " +
+                                                      std::to_string(all[4]) + ", rank " + std::to_string(r) + " " +
+                                                      std::to_string(all[5 * r + 4]) + ")");
+        }
+        if (plan_sample_argsort64(P, f.data(), c.data(), lo.data(), hi.data(), &pl))
+            return set_err(ctx, DSORT_EINVAL, "sample argsort: the ranks' key ranges overlap or end beyond 2^32");
+        if (forced && pl.total) pl.passes = 2;
+        if (pl.passes == 2 && P > 256)
+            return set_err(ctx, DSORT_EINVAL, "sample argsort: more than 256 ranks on the two-pass path (the gather's "
+                                              "owner table)");
+        if (pl.passes == 2 && pl.total >= (1ull << 32))
+            return set_err(ctx, DSORT_EINVAL, "sample argsort: 2^32 keys on the two-pass path (a slice is the index "
+                                              "array of a gather: fewer than 2^32)");
+        if (keep.stage >= 0 && pl.total) {
+            BxPlan bp;
+            stages = bx_make_plan(ctx->opt, P, call.me, c.data(), 8, bp) ? 3 : sort_stages(ctx->opt, n, 8);
+            never = keep.stage >= stages;
+        }
+    }
+    if (pl.total == 0) {  // no rank holds a key: nothing to sort, and no collective is left
+        ctx->stats = fresh_stats();
+        ctx->ev_mask = 0;
+        ctx->kev_used = 0;
+        if (keys_out) *keys_out = static_cast<int64_t *>(ctx->s64_k);
+        *idx_out = static_cast<uint32_t *>(ctx->s64_i);
+        *n_out = 0;
+        return DSORT_OK;
+    }
+    ahead = true;
+    sample_leg_event(ctx, s);
+    const bool wide = pl.passes == 2;
+    const unsigned grid = grid_for(((uint64_t)n + 3) / 4);
+
+    // the words of the first (narrow: the only) sort, positions from `first` on
+    if ((rc = ensure(ctx, &ctx->pairs, &ctx->pairs_bytes, (n ? n : 1) * 8, "pair arena"))) return fail(rc);
+    uint64_t *A = static_cast<uint64_t *>(ctx->pairs);
+    if (n) {
+        if (wide)
+            hipLaunchKernelGGL((pack64_kernel<true>), dim3(grid), dim3(NT), 0, s, keys, A, (uint64_t)n, (uint64_t)0, 0,
+                               first);
+        else
+            hipLaunchKernelGGL((pack64_kernel<false>), dim3(grid), dim3(NT), 0, s, keys, A, (uint64_t)n,
+                               (uint64_t)pl.kmin, pl.b, first);
+        if ((rc = launched(ctx, "pack64_kernel"))) return fail(rc);
+    }
+    sample_leg_event(ctx, s);
+
+    // leg 1.  A kill stage this sort never reaches would make it return early, DSORT_ESTAGE, with
+    // the peers in the legs that follow: switched off for it and reported at the end instead.
+    if ((rc = before_leg(1))) return rc;
+    if (never) ctx->opt.kill_after_pass = -1;
+    int64_t *sa = nullptr;
+    size_t mA = 0;
+    rc = sample_sort_packed(ctx, reinterpret_cast<const int64_t *>(A), n, &sa, &mA, stream);
+    ctx->opt.kill_after_pass = -1;  // (and off from here on: the second sort is not a kill point)
+    ctx->opt.kill_in_exchange = -1;
+    if (rc) return rc;  // (inside a leg: its own guard has told the peers)
+    ahead = wide;
+    if (mA && (reinterpret_cast<uintptr_t>(sa) & 15))
+        return fail(set_err(ctx, DSORT_EHIP, "sample argsort: the sample sort's slice is not 16-byte aligned"));
+    sample_leg_event(ctx, s);
+
+    size_t m = mA;
+    const uint64_t *SB = nullptr, *AW = nullptr;
+    if (wide) {
+        // the slice is saved (the second sort's output takes its place) and split: its low words
+        // are the positions of its keys
+        if ((rc = ensure(ctx, &ctx->s64_sa, &ctx->s64_sa_bytes, (mA ? mA : 1) * 8, "sample argsort saved slice")))
+            return fail(rc);
+        if ((rc = ensure(ctx, &ctx->s64_pos, &ctx->s64_pos_bytes, (mA ? mA : 1) * 4, "sample argsort indices")))
+            return fail(rc);
+        if ((rc = ensure(ctx, &ctx->s64_got, &ctx->s64_got_bytes, (mA ? mA : 1) * 8, "sample argsort gathered words")))
+            return fail(rc);
+        uint64_t *SA = static_cast<uint64_t *>(ctx->s64_sa);
+        uint32_t *pos = static_cast<uint32_t *>(ctx->s64_pos);
+        uint64_t *got = static_cast<uint64_t *>(ctx->s64_got);
+        const unsigned gA = grid_for(((uint64_t)mA + 3) / 4);
+        if (mA) {
+            hipLaunchKernelGGL(split64_kernel, dim3(gA), dim3(NT), 0, s, reinterpret_cast<const uint64_t *>(sa), SA, pos,
+                               (uint64_t)mA);
+            if ((rc = launched(ctx, "split64_kernel"))) return fail(rc);
+        }
+        sample_leg_event(ctx, s);
+
+        // leg 2: every rank's slice length; offA = the rank of this slice's first word in pass-A order
+        if ((rc = before_leg(2))) return rc;
+        uint64_t offA = 0;
+        {
+            ExchCall call(ctx, stream, 1);
+            if (call.rc) return call.rc;
+            const uint64_t mine = mA;
+            std::vector<uint64_t> all((size_t)P);
+            rc = allgather_u64(ctx, &mine, 1, all.data(), s, call.deadline, "sample argsort slice-length all-gather");
+            if (rc) return rc;
+            call.finished();
+            uint64_t sum = 0;
+            for (int r = 0; r < P; ++r) {
+                if (r == call.me) offA = sum;
+                sum += all[r];
+            }
+            if (sum != pl.total) {  // (the same on every rank)
+                ahead = false;
+                return set_err(ctx, DSORT_EHIP, "sample argsort: the slices of the first sort do not add up");
+            }
+        }
+
+        // leg 3: the whole keys in pass-A order, from wherever they live
+        if ((rc = before_leg(3))) return rc;
+        rc = dsort_sample_gather_dev(ctx, keys, n, first, pos, mA, got, 8, stream);
+        if (rc) return rc;
+        sample_leg_event(ctx, s);
+
+        // the second sort's words: the high halves over the ranks in pass-A order
+        if ((rc = ensure(ctx, &ctx->pairs, &ctx->pairs_bytes, (mA ? mA : 1) * 8, "pair arena"))) return fail(rc);
+        uint64_t *B = static_cast<uint64_t *>(ctx->pairs);
+        if (mA) {
+            hipLaunchKernelGGL(regroup_stream64_kernel, dim3(gA), dim3(NT), 0, s, got, B, (uint64_t)mA, (uint32_t)offA);
+            if ((rc = launched(ctx, "regroup_stream64_kernel"))) return fail(rc);
+        }
+        sample_leg_event(ctx, s);
+
+        // leg 4
+        if ((rc = before_leg(4))) return rc;
+        int64_t *sb = nullptr;
+        size_t mB = 0;
+        rc = sample_sort_packed(ctx, reinterpret_cast<const int64_t *>(B), mA, &sb, &mB, stream);
+        if (rc) return rc;
+        if (mB && (reinterpret_cast<uintptr_t>(sb) & 15))
+            return fail(set_err(ctx, DSORT_EHIP, "sample argsort: the sample sort's slice is not 16-byte aligned"));
+        sample_leg_event(ctx, s);
+        if ((rc = ensure(ctx, &ctx->s64_pos, &ctx->s64_pos_bytes, (mB ? mB : 1) * 4, "sample argsort indices")))
+            return fail(rc);
+        if ((rc = ensure(ctx, &ctx->s64_got, &ctx->s64_got_bytes, (mB ? mB : 1) * 8, "sample argsort gathered words")))
+            return fail(rc);
+        pos = static_cast<uint32_t *>(ctx->s64_pos);
+        got = static_cast<uint64_t *>(ctx->s64_got);
+        if (mB) {
+            hipLaunchKernelGGL(split64_kernel, dim3(grid_for(((uint64_t)mB + 3) / 4)), dim3(NT), 0, s,
+                               reinterpret_cast<const uint64_t *>(sb), static_cast<uint64_t *>(nullptr), pos, (uint64_t)mB);
+            if ((rc = launched(ctx, "split64_kernel"))) return fail(rc);
+        }
+        sample_leg_event(ctx, s);
+
+        // leg 5: every word of the slice gets its pass-A word, which rank offA' + j' of some rank holds
+        if ((rc = before_leg(5))) return rc;
+        rc = dsort_sample_gather_dev(ctx, SA, mA, offA, pos, mB, got, 8, stream);
+        if (rc) return rc;
+        ahead = false;
+        sample_leg_event(ctx, s);
+        m = mB;
+        SB = reinterpret_cast<const uint64_t *>(sb);
+        AW = got;
+    }
+
+    // this rank's slice into the output arenas
+    if (keys_out && (rc = ensure(ctx, &ctx->s64_k, &ctx->s64_k_bytes, (m ? m : 1) * 8, "sample argsort keys"))) return rc;
+    if ((rc = ensure(ctx, &ctx->s64_i, &ctx->s64_i_bytes, (m ? m : 1) * 4, "sample argsort positions"))) return rc;
+    int64_t *ko = keys_out ? static_cast<int64_t *>(ctx->s64_k) : nullptr;
+    uint32_t *io = static_cast<uint32_t *>(ctx->s64_i);
+    if (m) {
+        const unsigned g = grid_for(((uint64_t)m + 3) / 4);
+        if (wide)
+            hipLaunchKernelGGL(final_stream64_kernel, dim3(g), dim3(NT), 0, s, SB, AW, ko, io, (uint64_t)m);
+        else
+            hipLaunchKernelGGL(unpack64_kernel, dim3(g), dim3(NT), 0, s, reinterpret_cast<const uint64_t *>(sa), ko, io,
+                               (uint64_t)m, (uint64_t)pl.kmin, pl.b);
+        if ((rc = launched(ctx, "sample argsort unpack"))) return rc;
+    }
+    sample_leg_event(ctx, s);
+    ctx->stats.argsort_passes = pl.passes;
+    if ((rc = order_end(ctx, s))) return rc;
+    if (keys_out) *keys_out = ko;
+    *idx_out = io;
+    *n_out = m;
+    if (never)
+        return set_err(ctx, DSORT_ESTAGE,
+                       "DSORT_OPT_KILL_AFTER_STAGE = " + std::to_string(keep.stage) + ": the first sample sort of this " +
+                           "argsort has " + std::to_string(stages) + " stages (kill points 0.." +
+                           std::to_string(stages - 1) + "); every leg has run");
+    return DSORT_OK;
 }
 
 static int check_args(dsort_ctx *ctx, const void *keys, const void *out, size_t n) {
@@ -437,6 +817,26 @@ int dsort_sort_records_dev_i64(dsort_ctx *ctx, const int64_t *d_keys, int64_t *d
     return src ? set_err(ctx, src, msg) : DSORT_OK;
 }
 
+int dsort_sample_argsort_dev_i64(dsort_ctx *ctx, const int64_t *d_keys, size_t n_local, uint64_t first,
+                                 int64_t **d_keys_out, uint32_t **d_idx_out, size_t *n_out, void *stream) {
+    if (!ctx) return DSORT_EINVAL;
+    if (first > (1ull << 32) || (uint64_t)n_local > (1ull << 32) - first)
+        return set_err(ctx, DSORT_EINVAL,
+                       "sample argsort: first + n_local exceeds 2^32 (a global position must fit 32 bits)");
+    if (!d_idx_out || !n_out || (n_local && !d_keys)) return set_err(ctx, DSORT_EINVAL, "null argument");
+    return p64::sample_argsort64(ctx, d_keys, n_local, first, d_keys_out, d_idx_out, n_out, stream);
+}
+
+int dsort_plan_sample_argsort_i64(int nranks, const uint64_t first[], const uint64_t count[], const int64_t key_min[],
+                                  const int64_t key_max[], int *idx_bits, int *passes) {
+    if (nranks < 1 || !first || !count || !key_min || !key_max) return DSORT_EINVAL;
+    p64::SamplePlan pl;
+    if (int rc = p64::plan_sample_argsort64(nranks, first, count, key_min, key_max, &pl)) return rc;
+    if (idx_bits) *idx_bits = pl.b;
+    if (passes) *passes = pl.passes;
+    return DSORT_OK;
+}
+
 int dsort_argsort_i64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uint32_t *idx, size_t n) {
     if (!ctx) return DSORT_EINVAL;
     if (int rc = p64::check_args(ctx, keys, idx, n)) return rc;
@@ -473,6 +873,26 @@ int dsort_argsort64_leg_ms(dsort_ctx *ctx, double ms[6], int *legs) {
     for (int i = first; i < nl; ++i) {
         float f = 0;
         DSORT_HIP(ctx, hipEventElapsedTime(&f, ctx->a64_ev[i - first], ctx->a64_ev[i - first + 1]));
+        ms[i] = f;
+    }
+    *legs = nl;
+    return DSORT_OK;
+}
+
+// The same for the last dsort_sample_argsort_dev_i64 (scripts/bench_pairs.py --sample-i64); the time
+// between two events includes the host waits of what lies between them.  One pass, *legs = 4:
+// decision (min/max, all-gather), pack, sample sort, unpack.  Two passes, *legs = 10: decision, pack,
+// sample sort 1, split, key gather (the slice-length all-gather included), regroup, sample sort 2,
+// split, final gather, final.  ms must hold 10.  DSORT_EINVAL when the call recorded none.
+int dsort_sample_argsort64_leg_ms(dsort_ctx *ctx, double ms[10], int *legs) {
+    if (!ctx || !ms || !legs) return DSORT_EINVAL;
+    const int nl = ctx->s64_legs - 1;
+    if (!ctx->s64_ev_ok || (nl != 4 && nl != 10))
+        return set_err(ctx, DSORT_EINVAL, "no timed int64 sample argsort on this context");
+    DSORT_HIP(ctx, hipEventSynchronize(ctx->s64_ev[nl]));
+    for (int i = 0; i < nl; ++i) {
+        float f = 0;
+        DSORT_HIP(ctx, hipEventElapsedTime(&f, ctx->s64_ev[i], ctx->s64_ev[i + 1]));
         ms[i] = f;
     }
     *legs = nl;

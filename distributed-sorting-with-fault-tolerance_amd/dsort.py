@@ -47,6 +47,7 @@ EXPORTS = [
     "dsort_sample_argsort_dev_i32", "dsort_sample_sort_pairs_dev_i32",
     "dsort_sample_gather_dev", "dsort_plan_gather_table", "dsort_plan_gather_route",
     "dsort_argsort_dev_i64", "dsort_argsort_i64", "dsort_sort_records_dev_i64", "dsort_plan_argsort_i64",
+    "dsort_sample_argsort_dev_i64", "dsort_plan_sample_argsort_i64",
 ]
 
 
@@ -56,7 +57,7 @@ OPTIONS = {"buckets": 1, "bucket_keys": 2, "bucket_oversample": 3,
            "comm_timeout_ms": 8,
            "sub_keys": 9, "sub_oversample": 10, "sub_gather": 11, "test_hold_exchange": 12,
            "test_fail_exchange": 13, "stage_timing": 14, "test_tile_cap": 15,
-           "test_wave_fence": 16, "argsort_wide": 17}
+           "test_wave_fence": 16, "argsort_wide": 17, "test_fail_leg": 18}
 
 
 class DsortError(RuntimeError):
@@ -277,6 +278,10 @@ def load():
         "dsort_sort_records_dev_i64": (ctypes.c_int, [P, P, P, P, P, SZ, ctypes.c_int, P]),
         "dsort_plan_argsort_i64": (ctypes.c_int, [SZ, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int),
                                                   ctypes.POINTER(ctypes.c_int)]),
+        "dsort_sample_argsort_dev_i64": (ctypes.c_int, [P, P, SZ, U64, ctypes.POINTER(P), ctypes.POINTER(P),
+                                                        ctypes.POINTER(SZ), P]),
+        "dsort_plan_sample_argsort_i64": (ctypes.c_int, [ctypes.c_int, P, P, P, P, ctypes.POINTER(ctypes.c_int),
+                                                         ctypes.POINTER(ctypes.c_int)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -371,6 +376,21 @@ def plan_argsort_i64(n, key_min, key_max):
     smallest and largest are key_min and key_max."""
     b, p = ctypes.c_int(), ctypes.c_int()
     _check(None, load().dsort_plan_argsort_i64(n, key_min, key_max, ctypes.byref(b), ctypes.byref(p)))
+    return b.value, p.value
+
+
+def plan_sample_argsort_i64(first, count, key_min, key_max):
+    """The host rule of the int64 argsort across ranks (dsort_plan_sample_argsort_i64):
+    (idx_bits, passes) from every rank's range [first[r], first[r] + count[r]) and the smallest and
+    largest key it holds (ignored where count[r] is 0)."""
+    first = np.ascontiguousarray(first, np.uint64)
+    count = np.ascontiguousarray(count, np.uint64)
+    key_min = np.ascontiguousarray(key_min, np.int64)
+    key_max = np.ascontiguousarray(key_max, np.int64)
+    assert count.size == first.size == key_min.size == key_max.size
+    b, p = ctypes.c_int(), ctypes.c_int()
+    _check(None, load().dsort_plan_sample_argsort_i64(first.size, _ptr(first), _ptr(count), _ptr(key_min),
+                                                      _ptr(key_max), ctypes.byref(b), ctypes.byref(p)))
     return b.value, p.value
 
 
@@ -719,30 +739,39 @@ class Context:
         return outp.value or 0, nout.value
 
     # ---------------- argsort and key-value sort across ranks (int32 keys; dsort.h, ABI 8) ----
-    def _slices(self, ptrs, n, device):
-        """Fresh int32 tensors holding the context-owned slices at `ptrs` (n elements each).  The
-        unpack that fills them was queued on torch's current stream and dsort_copy_d2d runs on the
-        context's: the stream is drained first."""
+    def _slices(self, ptrs, n, device, dtypes=None):
+        """Fresh tensors (int32, or `dtypes`) holding the context-owned slices at `ptrs` (n elements
+        each).  The unpack that fills them was queued on torch's current stream and dsort_copy_d2d
+        runs on the context's: the stream is drained first."""
         torch.cuda.current_stream().synchronize()
         outs = []
-        for p in ptrs:
-            t = torch.empty(n, dtype=torch.int32, device=device)
+        for p, dt in zip(ptrs, dtypes or [torch.int32] * len(ptrs)):
+            t = torch.empty(n, dtype=dt, device=device)
             if n:
-                self.check(self.lib.dsort_copy_d2d(self.h, t.data_ptr(), p.value, 4 * n))
+                self.check(self.lib.dsort_copy_d2d(self.h, t.data_ptr(), p.value, t.element_size() * n))
             outs.append(t)
         return outs
 
     def sample_argsort_dev(self, keys, first):
-        """Global stable argsort over the communicator (dsort_sample_argsort_dev_i32): `keys` is
-        this rank's chunk, holding the global positions first .. first + len(keys) - 1.  Returns
-        (sorted_keys, idx), this rank's slice of the global order as fresh int32 CUDA tensors; idx
-        holds global positions as uint32 bit patterns, as argsort_dev documents."""
-        n = self._i32(keys, "keys").numel()
+        """Global stable argsort over the communicator (dsort_sample_argsort_dev_i32 / _i64): `keys`
+        is this rank's chunk, int32 or int64, holding the global positions first .. first +
+        len(keys) - 1.  Returns (sorted_keys, idx), this rank's slice of the global order as fresh
+        CUDA tensors: the keys of the input's type, idx int32 holding global positions as uint32 bit
+        patterns, as argsort_dev documents.  DSORT_ESTAGE of the int64 call leaves valid outputs: the
+        DsortError then carries them as `.slices`."""
+        kt = torch.int64 if keys.dtype == torch.int64 else torch.int32
+        n = self._i32(keys, "keys", dtype=kt).numel()
         kp, ip, nout = P(), P(), SZ()
-        self.check(self.lib.dsort_sample_argsort_dev_i32(self.h, keys.data_ptr() if n else None, n, int(first),
-                                                         ctypes.byref(kp), ctypes.byref(ip), ctypes.byref(nout),
-                                                         self._stream()))
-        k, i = self._slices((kp, ip), nout.value, keys.device)
+        f = self.lib.dsort_sample_argsort_dev_i64 if kt == torch.int64 else self.lib.dsort_sample_argsort_dev_i32
+        rc = f(self.h, keys.data_ptr() if n else None, n, int(first), ctypes.byref(kp), ctypes.byref(ip),
+               ctypes.byref(nout), self._stream())
+        try:
+            self.check(rc)
+        except DsortError as e:
+            if e.rc == -7 and kt == torch.int64:  # DSORT_ESTAGE: every leg has run
+                e.slices = tuple(self._slices((kp, ip), nout.value, keys.device, (kt, torch.int32)))
+            raise
+        k, i = self._slices((kp, ip), nout.value, keys.device, (kt, torch.int32))
         return k, i
 
     def sample_sort_pairs_dev(self, keys, vals):
@@ -786,7 +815,7 @@ class Context:
         return out
 
     def sample_sort_records_dev(self, keys, records, first):
-        """Distributed sort of records by an int32 key: sample_argsort_dev, then sample_gather_dev
+        """Distributed sort of records by an int32 or int64 key: sample_argsort_dev, then sample_gather_dev
         with the returned indices.  keys[i] is the key of records[i], global position first + i.
         Returns (sorted_keys, records_of_my_slice)."""
         if int(records.shape[0]) != keys.numel():

@@ -183,7 +183,15 @@ int dsort_synchronize(dsort_ctx *ctx);
                                          keys' range allows it, else two (default; the call then reads
                                          the keys' min and max first and waits for them on the host);
                                          1 = always two passes (correct on any input, no host wait):
-                                         for tests and for the bench's A/B of the two paths          */
+                                         for tests and for the bench's A/B of the two paths.  Across
+                                         ranks (dsort_sample_argsort_dev_i64) every rank must set
+                                         the same value                                              */
+#define DSORT_OPT_TEST_FAIL_LEG 18     /* test only (an ABI 10 addition): k >= 0 = this rank fails
+                                         locally with DSORT_EHIP right before leg k of
+                                         dsort_sample_argsort_dev_i64 (0 decision, 1 first sort, 2
+                                         slice-length all-gather, 3 key gather, 4 second sort, 5 final
+                                         gather); a leg the call never reaches is ignored.  -1 = off
+                                         (default)                                                   */
 int dsort_set_option(dsort_ctx *ctx, int option, int64_t value);
 int dsort_get_option(const dsort_ctx *ctx, int option, int64_t *value);
 
@@ -401,9 +409,9 @@ int dsort_sample_merge_dev_i64(dsort_ctx *ctx, const int64_t *d_sorted, size_t n
  * without the keys), all grow-only, on top of the int64 sample sort's memory for these counts.
  *
  * Wider payload records reach the rank that holds their key through dsort_sample_gather_dev (ABI 9,
- * below).  Not offered across ranks: int64 keys with a payload (one GPU: ABI 10); the presorted /
- * fault-survivor entry (dsort_sample_merge_dev_*) for pairs; the C master and workers, which move
- * bare keys. */
+ * below); int64 keys take dsort_sample_argsort_dev_i64 and the same gather.  Not offered across
+ * ranks: the presorted / fault-survivor entry (dsort_sample_merge_dev_*) for pairs; the C master and
+ * workers, which move bare keys. */
 
 /* Global stable argsort.  The rank's chunk d_keys[0..n_local) holds the global positions
  * first .. first + n_local - 1 (`first` as in dsort_gen_uniform_*); (*d_idx_out)[j] is the global
@@ -417,6 +425,74 @@ int dsort_sample_argsort_dev_i32(dsort_ctx *ctx, const int32_t *d_keys, size_t n
 int dsort_sample_sort_pairs_dev_i32(dsort_ctx *ctx, const int32_t *d_keys, const uint32_t *d_vals,
                                     size_t n_local, int32_t **d_keys_out, uint32_t **d_vals_out,
                                     size_t *n_out, void *stream);
+
+/* An ABI 10 addition (new symbols only): the global stable argsort of int64 keys, and with
+ * dsort_sample_gather_dev the record sort of int64 keys across ranks.  The contract of
+ * dsort_sample_argsort_dev_i32: collective, a rank with n_local == 0 (d_keys may be NULL) joins every
+ * collective; the inputs are not modified; d_keys_out may be NULL (keys not wanted); *d_keys_out
+ * (int64) and *d_idx_out (uint32 global positions) are context-owned arrays of *n_out elements in
+ * arenas of this call's own, ready after `stream` and valid until the next sample sort, pair call
+ * or argsort call on the context (a gather invalidates nothing) or dsort_finalize; concatenating the
+ * slices of ranks 0..nranks-1 gives the keys ascending, equal keys in ascending global position.
+ * Keys need 8-byte alignment only.
+ *
+ * Algorithm.  Every rank takes the same branch, decided in leg 0: one all-gather of every rank's
+ * (first, n_local, local min, local max, DSORT_OPT_ARGSORT_WIDE), to which every rank applies
+ * dsort_plan_sample_argsort_i64.  The min and max come from the local argsort's reduction and one
+ * host wait; a rank without keys, or with the option set, skips it.
+ *   narrow, 1 pass     the local argsort's narrow word with b from E = the end of the global range
+ *                      and the GLOBAL minimum, position = first + i, through the int64 sample sort
+ *                      (leg 1); the slice is unpacked into the output arenas.
+ *   wide, 2 passes     least significant half first.  A = (lo32 ^ 0x80000000) : (first + i) through
+ *                      the sample sort (leg 1) gives the slice SA of mA words, which is saved; the
+ *                      ranks all-gather mA (leg 2; offA = the exclusive prefix); a distributed
+ *                      gather of the caller's keys by SA's low words (leg 3) gives the whole keys in
+ *                      pass-A order; B[j] = hi32 : (offA + j) goes through the sample sort (leg 4);
+ *                      a gather of the saved SA by SB's low words (leg 5) brings every SB word its SA
+ *                      word: index = its low word, key = hi32(SB) : (hi32(SA) ^ 0x80000000).
+ * All words of both sorts are distinct, so a heavy key splits between ranks by position.
+ *
+ * Limits: first + n_local <= 2^32 (else DSORT_EINVAL before any memory or collective is touched);
+ * on the wide path fewer than 2^32 keys in all (a slice is the index array of a gather) and at most
+ * 256 ranks (the gather's owner table) -- both DSORT_EINVAL on every rank after leg 0.
+ *
+ * Errors.  Checked symmetrically in leg 0 -- every rank returns DSORT_EINVAL from the same call and
+ * the communicator stays usable: ranks that disagree on DSORT_OPT_ARGSORT_WIDE, two non-empty ranges
+ * that overlap.  Every leg is an exchange call of its own with the host transport's status gates,
+ * the deadline (DSORT_OPT_COMM_TIMEOUT_MS, per leg) and dsort_comm_abort as in a sample sort; a rank
+ * that fails locally BETWEEN two legs (an arena, a kernel launch, DSORT_OPT_TEST_FAIL_LEG) reports
+ * at the gate of the next leg, so its peers return DSORT_ECOMM naming it instead of blocking (RCCL
+ * has no gates: the deadline and the abort flag).  DSORT_OPT_TEST_FAIL_EXCHANGE = k counts the
+ * collectives of each leg from 0 and fires in the first leg that reaches collective k.
+ * DSORT_OPT_KILL_AFTER_STAGE and DSORT_OPT_KILL_IN_EXCHANGE act inside the FIRST inner sample sort,
+ * as on dsort_sample_sort_dev_i64 of the same counts, and are off during the second.  A kill stage
+ * beyond that sort's stages (dsort_sample_sort_stages; with DSORT_OPT_SUB_KEYS = 0 its guaranteed
+ * minimum) does not stop the call, whose peers are in the legs that follow: every leg runs, the
+ * outputs are valid and the call returns DSORT_ESTAGE at the end.
+ *
+ * dsort_get_stats: argsort_passes = 1 or 2 (0: no keys on any rank), the other fields as the last
+ * inner sample sort left them.
+ *
+ * Memory (context arenas, grow-only), with n = n_local, m = this rank's slice (mA, mB on the wide
+ * path): the pair arena 8 max(n, mA), the outputs 12 m (4 m without the keys); wide: 8 mA for the
+ * saved slice, 4 max(mA, mB) of indices and 8 max(mA, mB) of gathered words; on top of the int64
+ * sample sort's and the gather's memory for these counts.
+ *
+ * The RCCL path has run with one rank only. */
+int dsort_sample_argsort_dev_i64(dsort_ctx *ctx, const int64_t *d_keys, size_t n_local, uint64_t first,
+                                 int64_t **d_keys_out, uint32_t **d_idx_out, size_t *n_out,
+                                 void *stream);
+/* The host rule of leg 0, exported so that the CPU tests run the code the GPU path runs.  Ranks with
+ * count[r] == 0 are ignored, their key_min / key_max included.  With E = the largest
+ * first[r] + count[r] and the smallest key_min / largest key_max over the other ranks, the result
+ * is that of dsort_plan_argsort_i64(E, min, max): b comes from E, not from the key count, so that
+ * every global position fits b bits.  All counts 0: 0 passes (b = 1).  DSORT_EINVAL: nranks < 1, a
+ * NULL array, two non-empty ranges that overlap or one that ends beyond 2^32
+ * (dsort_plan_gather_table's rule), a non-empty rank with key_min > key_max.  Either output may be
+ * NULL. */
+int dsort_plan_sample_argsort_i64(int nranks, const uint64_t first[], const uint64_t count[],
+                                  const int64_t key_min[], const int64_t key_max[], int *idx_bits,
+                                  int *passes);
 
 /* ABI 9: the distributed record gather -- payloads follow their keys across ranks.
  *   d_dst[j] = the record at GLOBAL position d_idx[j], j < n_idx, wherever it lives.

@@ -41,6 +41,15 @@ check, bit for bit), the narrow keys again with DSORT_OPT_ARGSORT_WIDE = 1, each
 fraction of a device-to-device copy of the same byte total, and the two random-access legs against
 dsort_gather_dev of 8-byte records over a random permutation of the same n (bench_i64).
 
+    python scripts/bench_pairs.py --sample-i64 [--log2 28] [--steps 10] [--out profiles/pairs_sample_i64_bench.json]
+
+--sample-i64 measures the global argsort of int64 keys (dsort_sample_argsort_dev_i64) on one RCCL rank,
+on the narrow and the wide keys of --i64, against dsort_argsort_dev_i64 on the same keys in the same
+process, results compared bit for bit: ms per call, the legs of both from the library's HIP events
+(dsort_sample_argsort64_leg_ms: 4 legs on one pass, 10 on two), and its streaming kernels -- pack,
+unpack, the two splits, regroup, final -- as fractions of a device-to-device copy of the same byte
+total in the same run (bench_sample_i64).
+
 Writes the JSON file and prints one summary line.  No GPU: fails (there is nothing to measure).
 """
 import argparse
@@ -368,6 +377,90 @@ def bench_i64(torch, ctx, n, steps, warmup):
             "leg_bytes_per_element": I64_LEG_BYTES, "inputs": inputs}
 
 
+# HBM bytes per element of the streaming kernels of the int64 argsort across ranks (keys wanted)
+S64_LEG_BYTES = {"pack": 16, "unpack": 20, "split_save": 20, "regroup": 16, "split": 12, "final": 28}
+S64_LEG_NAMES = {4: ("decision", "pack", "sample_sort", "unpack"),
+                 10: ("decision", "pack", "sample_sort_lo", "split_save", "key_gather", "regroup", "sample_sort_hi",
+                      "split", "final_gather", "final")}
+
+
+def bench_sample_i64(torch, dsort, ctx, n, steps, warmup):
+    """--sample-i64: dsort_sample_argsort_dev_i64 on ONE RCCL rank, narrow and wide keys, against
+    dsort_argsort_dev_i64 on the same keys in the same process, results compared bit for bit.  One
+    rank ships nothing, and there is no shortcut: every leg runs, so the wide path pays two
+    distributed gathers where the local call pays two random-read kernels."""
+    ctx.comm_init(1, 0, dsort.Context.unique_id())
+    leg_fn = ctx.lib.dsort_sample_argsort64_leg_ms  # not in dsort.h: the bench's view of the legs' events
+    leg_fn.restype = ctypes.c_int
+    leg_fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
+    loc_fn = ctx.lib.dsort_argsort64_leg_ms
+    loc_fn.restype = ctypes.c_int
+    loc_fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
+    r4 = lambda x: round(x, 4)  # noqa: E731
+    gbs = lambda b, ms: b / (ms * 1e-3) / 1e9  # noqa: E731
+    keys = torch.empty(n, dtype=torch.int64, device="cuda")
+    out = torch.empty_like(keys)
+    idx = torch.empty(n, dtype=torch.int32, device="cuda")
+    kp, ip, nout = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+
+    def sample():  # the C entry itself: the binding's copies into fresh tensors are not part of it
+        ctx.check(ctx.lib.dsort_sample_argsort_dev_i64(ctx.h, keys.data_ptr(), n, 0, ctypes.byref(kp),
+                                                       ctypes.byref(ip), ctypes.byref(nout), ctx._stream()))
+
+    def local():
+        ctx.argsort_dev(keys, idx_out=idx, keys_out=out)
+
+    def legs_of(fn, hook, room, names):
+        legs = []
+        for _ in range(steps):
+            fn()
+            buf, cnt = (ctypes.c_double * room)(), ctypes.c_int()
+            ctx.check(hook(ctx.h, buf, ctypes.byref(cnt)))
+            legs.append(tuple(buf[:cnt.value]))
+        return {k: r4(statistics.median(x[i] for x in legs)) for i, k in enumerate(names[len(legs[0])])}
+
+    copies = {}
+    for total in sorted(set(S64_LEG_BYTES.values())):
+        src = torch.empty(total * n // 2, dtype=torch.uint8, device="cuda")
+        dst = torch.empty_like(src)
+        src.zero_()
+        copies[total] = timed(torch, lambda: dst.copy_(src), steps, warmup)
+        del src, dst
+        torch.cuda.empty_cache()
+
+    inputs = {}
+    for name in ("narrow", "wide"):
+        ctx.gen_uniform(keys, 0x5EED2026, 0)
+        if name == "narrow":
+            keys >>= 30  # arithmetic: uniform in [-2^33, 2^33)
+        local_ms = timed(torch, local, steps, warmup)
+        local_legs = legs_of(local, loc_fn, 6, I64_LEG_NAMES)
+        sample_ms = timed(torch, sample, steps, warmup)
+        sample_legs = legs_of(sample, leg_fn, 10, S64_LEG_NAMES)
+        st = ctx.stats()
+        sk, si = ctx.sample_argsort_dev(keys, 0)  # (the check, through the binding)
+        local()
+        torch.cuda.synchronize()
+        exact = bool(sk.numel() == n and torch.equal(sk, out) and torch.equal(si, idx))
+        del sk, si
+        torch.cuda.empty_cache()
+        streaming = {}
+        for leg, ms in sample_legs.items():
+            if leg in S64_LEG_BYTES and ms > 0:
+                total = S64_LEG_BYTES[leg]
+                streaming[leg] = {"bytes": total * n, "gb_per_s": r4(gbs(total * n, ms)), "memcpy_ms": r4(copies[total]),
+                                  "memcpy_gb_per_s": r4(gbs(total * n, copies[total])),
+                                  "frac_of_memcpy": r4(copies[total] / ms)}
+        inputs[name] = {"sample_argsort_ms": r4(sample_ms), "local_argsort_ms": r4(local_ms),
+                        "sample_over_local": r4(sample_ms / local_ms), "argsort_passes": st["argsort_passes"],
+                        "sample_legs_ms": sample_legs, "sample_legs_sum_ms": r4(sum(sample_legs.values())),
+                        "local_legs_ms": local_legs, "streaming": streaming,
+                        "last_sample_sort_stats": {k: st[k] for k in ("exchange_path", "total_ms", "keys_out")},
+                        "exact_vs_local_argsort": exact}
+    ctx.comm_destroy()
+    return {"n": n, "leg_bytes_per_element": S64_LEG_BYTES, "inputs": inputs}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2", type=int, nargs="+", default=None)
@@ -382,11 +475,15 @@ def main():
     ap.add_argument("--i64", action="store_true",
                     help="time dsort_argsort_dev_i64 on narrow, wide and Zipf keys against torch.sort(stable=True) "
                          "(default 2^28 and 2^30 keys, profiles/pairs_i64_bench.json)")
+    ap.add_argument("--sample-i64", action="store_true",
+                    help="time dsort_sample_argsort_dev_i64 on one RCCL rank, narrow and wide keys, against "
+                         "dsort_argsort_dev_i64 (default 2^28 keys, profiles/pairs_sample_i64_bench.json)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.log2 = args.log2 or ([28] if args.sample or args.gather else [28, 30])
+    args.log2 = args.log2 or ([28] if args.sample or args.gather or args.sample_i64 else [28, 30])
     name = "pairs_gather_bench.json" if args.gather else "pairs_sample_bench.json" if args.sample else "pairs_bench.json"
     name = "pairs_i64_bench.json" if args.i64 else name
+    name = "pairs_sample_i64_bench.json" if args.sample_i64 else name
     args.out = args.out or os.path.join(REPO, "profiles", name)
 
     import torch
@@ -396,6 +493,27 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_pairs: no GPU visible (nothing is measured without one)")
     ctx = dsort.Context(0)
+    if args.sample_i64:
+        res = {"what": "global stable argsort of int64 keys on one RCCL rank (dsort_sample_argsort_dev_i64): narrow = "
+                       "uniform in [-2^33, 2^33), one pass; wide = uniform over 64 bits, two passes with two distributed "
+                       "gathers; against dsort_argsort_dev_i64 of the same resident keys, same process; ms per call of "
+                       "--steps back-to-back calls, legs from the HIP events between them (median; they include the "
+                       "host waits between them), streaming kernels against a device-to-device copy of the same bytes",
+               "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup,
+               "sizes": [bench_sample_i64(torch, dsort, ctx, 1 << lg, args.steps, args.warmup) for lg in args.log2]}
+        ctx.close()
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"pairs_sample_i64_bench": [
+            {"n": s["n"], **{k: {"sample_argsort_ms": v["sample_argsort_ms"], "local_argsort_ms": v["local_argsort_ms"],
+                                 "sample_over_local": v["sample_over_local"], "passes": v["argsort_passes"],
+                                 "legs_ms": v["sample_legs_ms"],
+                                 "frac_of_memcpy": {g: w["frac_of_memcpy"] for g, w in v["streaming"].items()},
+                                 "exact": v["exact_vs_local_argsort"]} for k, v in s["inputs"].items()}}
+            for s in res["sizes"]]}), flush=True)
+        return
     if args.i64:
         res = {"what": "stable argsort of int64 keys, resident in HBM (dsort_argsort_dev_i64, sorted keys and indices): "
                        "narrow = uniform in [-2^33, 2^33), wide = uniform over 64 bits, zipf_c4 = dsort_gen_zipf_i64; ms "
