@@ -397,7 +397,7 @@ int dsort_finalize(dsort_ctx *ctx) {
                     ctx->bucket, ctx->sub, ctx->sub_alt, ctx->stmp, ctx->bxs, ctx->tfb, ctx->fence, ctx->pairs,
                     ctx->spairs_k, ctx->spairs_v, ctx->gat_req, ctx->gat_rreq, ctx->gat_rep, ctx->gat_back,
                     ctx->gat_small, ctx->a64_b, ctx->a64_idx, ctx->a64_part, ctx->s64_k, ctx->s64_i,
-                    ctx->s64_sa, ctx->s64_pos, ctx->s64_got};
+                    ctx->s64_sa, ctx->s64_pos, ctx->s64_got, ctx->kenc};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->red_host) (void)hipHostFree(ctx->red_host);

@@ -137,6 +137,10 @@ struct dsort_ctx {
     hipEvent_t s64_ev[kS64Ev] = {};  // around its legs (created on first use)
     int s64_legs = 0;             // ... those the last call recorded
     bool s64_ev_ok = false;       // ... all of them
+    // the typed-key sample sort and sample argsort (dsort_keys.hip): this rank's chunk, encoded -- the
+    // input of the integer call behind them
+    void *kenc = nullptr;
+    size_t kenc_bytes = 0;
     // the distributed gather (dsort_gather.hip): arenas of its own, so that a gather leaves the
     // slices of the preceding sample sort / argsort (recv2, spairs_k, spairs_v) alone
     void *gat_req = nullptr;      // this rank's requests, owner-major (4 B per index)
@@ -306,6 +310,18 @@ int order_end(dsort_ctx *ctx, hipStream_t s);
 // of the exchange layer: dsort_exch.h).  Takes the comm mutex itself: the caller must not hold it.
 int sample_sort_packed(dsort_ctx *ctx, const int64_t *d_in, size_t n_local, int64_t **d_out, size_t *n_out,
                        void *stream);
+// The pair sort of 4-byte keys (dsort_pairs.hip) and the argsort of 8-byte keys (dsort_pairs64.hip)
+// behind the argument checks of their entry points, for the typed-key entry points
+// (dsort_keys.hip).  kc = the key codec (dsort_keycodec.h), 0 = the signed integer, ascending; the
+// key pointers are typed as the integer of the key's width whatever the key type.
+namespace pr {
+int pairs_sort(dsort_ctx *ctx, const int32_t *keys_in, const uint32_t *vals_in, int32_t *keys_out,
+               uint32_t *vals_out, size_t n, hipStream_t s, int kc = 0);
+}
+namespace p64 {
+int argsort64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uint32_t *idx_out, size_t n, hipStream_t s,
+              int kc = 0);
+}
 // Host waits of the sort: blocking, or (ctx->poll_waits) polling with the abort flag and deadline
 // (DSORT_ECOMM / DSORT_ETIMEOUT).
 int sync_event(dsort_ctx *ctx, hipEvent_t e, const char *what);

@@ -27,6 +27,7 @@
 #include <string>
 
 #include "dsort_internal.h"
+#include "dsort_keycodec.h"
 
 namespace dsort {
 namespace pr {
@@ -53,11 +54,16 @@ typedef uint32_t u2_a4 __attribute__((ext_vector_type(2), aligned(4)));
 // 32 bytes apart, so that every store instruction fills half of each line it touches -- measured
 // 3.73 against 2.60 ms at 2^30 keys, 0.84 against 0.61 ms at 2^28, 2 of 2 alternating runs;
 // DESIGN.md 3.9.)
-template <bool ARG>
-__global__ void __launch_bounds__(NT) pairs_pack_kernel(const int32_t *__restrict__ keys,
-                                                        const uint32_t *__restrict__ vals,
-                                                        uint64_t *__restrict__ packed, uint64_t n,
-                                                        uint32_t base) {
+//
+// KC is the key codec (dsort_keycodec.h): the caller's keys are encoded as they are read.  The
+// body is shared by two kernels so that the int32 entry points keep launching the kernel they
+// always have (the identity codec: the same name, the same machine code) and the typed ones
+// (dsort_keys.hip) a kernel per codec.
+// (The pointers are the kernels' __restrict__ parameters.)
+template <bool ARG, int KC>
+__device__ __forceinline__ void pairs_pack_body(const int32_t *keys, const uint32_t *vals, uint64_t *packed,
+                                                uint64_t n, uint32_t base) {
+    using C = kc::Codec<KC>;
     const uint64_t chunks = n >> 8;
     const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
     const uint64_t nwaves = ((uint64_t)gridDim.x * NT) >> 6;
@@ -74,16 +80,68 @@ __global__ void __launch_bounds__(NT) pairs_pack_kernel(const int32_t *__restric
             v0 = *reinterpret_cast<const u2_a4 *>(vals + e0);
             v1 = *reinterpret_cast<const u2_a4 *>(vals + e1);
         }
-        __builtin_nontemporal_store(l2{pack1((int32_t)k0.x, v0.x), pack1((int32_t)k0.y, v0.y)},
-                                    reinterpret_cast<l2 *>(packed + e0));
-        __builtin_nontemporal_store(l2{pack1((int32_t)k1.x, v1.x), pack1((int32_t)k1.y, v1.y)},
-                                    reinterpret_cast<l2 *>(packed + e1));
+        __builtin_nontemporal_store(
+            l2{pack1((int32_t)C::enc(k0.x), v0.x), pack1((int32_t)C::enc(k0.y), v0.y)},
+            reinterpret_cast<l2 *>(packed + e0));
+        __builtin_nontemporal_store(
+            l2{pack1((int32_t)C::enc(k1.x), v1.x), pack1((int32_t)C::enc(k1.y), v1.y)},
+            reinterpret_cast<l2 *>(packed + e1));
     }
     const uint64_t i = (chunks << 8) + t;  // the n % 256 last elements, one each
-    if (i < n) packed[i] = pack1(keys[i], ARG ? base + (uint32_t)i : vals[i]);
+    if (i < n) packed[i] = pack1((int32_t)C::enc((uint32_t)keys[i]), ARG ? base + (uint32_t)i : vals[i]);
 }
 
-// keys_out[i] = high word, vals_out[i] = low word of packed[i]; a NULL output is not written
+template <bool ARG>
+__global__ void __launch_bounds__(NT) pairs_pack_kernel(const int32_t *__restrict__ keys,
+                                                        const uint32_t *__restrict__ vals,
+                                                        uint64_t *__restrict__ packed, uint64_t n,
+                                                        uint32_t base) {
+    pairs_pack_body<ARG, 0>(keys, vals, packed, n, base);
+}
+
+template <bool ARG, int KC>
+__global__ void __launch_bounds__(NT) pairs_pack_keys_kernel(const int32_t *__restrict__ keys,
+                                                             const uint32_t *__restrict__ vals,
+                                                             uint64_t *__restrict__ packed, uint64_t n,
+                                                             uint32_t base) {
+    pairs_pack_body<ARG, KC>(keys, vals, packed, n, base);
+}
+
+// keys_out[i] = high word (decoded by the codec KC), vals_out[i] = low word of packed[i]; a NULL
+// output is not written
+template <int KC>
+__global__ void __launch_bounds__(NT) pairs_unpack_keys_kernel(const uint64_t *__restrict__ packed,
+                                                               int32_t *__restrict__ keys_out,
+                                                               uint32_t *__restrict__ vals_out, uint64_t n) {
+    using C = kc::Codec<KC>;
+    const uint64_t groups = n >> 2;
+    const uint64_t stride = (uint64_t)gridDim.x * NT;
+    const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
+    for (uint64_t g = t; g < groups; g += stride) {
+        const uint64_t i = g << 2;
+        const l2 *src = reinterpret_cast<const l2 *>(packed + i);
+        const l2 a = src[0], b = src[1];
+        if (keys_out) {
+            const u4_a4 k = {C::dec((uint32_t)(a.x >> 32)), C::dec((uint32_t)(a.y >> 32)),
+                             C::dec((uint32_t)(b.x >> 32)), C::dec((uint32_t)(b.y >> 32))};
+            __builtin_nontemporal_store(k, reinterpret_cast<u4_a4 *>(keys_out + i));
+        }
+        if (vals_out) {
+            const u4_a4 v = {(uint32_t)a.x, (uint32_t)a.y, (uint32_t)b.x, (uint32_t)b.y};
+            __builtin_nontemporal_store(v, reinterpret_cast<u4_a4 *>(vals_out + i));
+        }
+    }
+    const uint64_t i = (groups << 2) + t;
+    if (i < n) {
+        const uint64_t p = packed[i];
+        if (keys_out) keys_out[i] = (int32_t)C::dec((uint32_t)(p >> 32));
+        if (vals_out) vals_out[i] = (uint32_t)p;
+    }
+}
+
+// The same without a codec: the kernel of the int32 entry points, kept word for word.  (As one body
+// shared with the kernel above, its instructions came out of the compiler in a slightly different
+// order; scripts/asm_digest.py compares it with the parent's.)
 __global__ void __launch_bounds__(NT) pairs_unpack_kernel(const uint64_t *__restrict__ packed,
                                                           int32_t *__restrict__ keys_out,
                                                           uint32_t *__restrict__ vals_out, uint64_t n) {
@@ -111,6 +169,7 @@ __global__ void __launch_bounds__(NT) pairs_unpack_kernel(const uint64_t *__rest
         if (vals_out) vals_out[i] = (uint32_t)p;
     }
 }
+
 
 // dst[i] = src[idx[i]] for records of W bytes (4, 8, 16): a lane takes the 16 / W records of one
 // 16-byte store.  Records are dword-aligned like everything of the caller's.
@@ -154,10 +213,20 @@ static bool leg_event(dsort_ctx *ctx, int i, hipStream_t s) {
     return hipEventRecord(ctx->pairs_ev[i], s) == hipSuccess;
 }
 
+// The launches of the typed kernels, defined at the end of the file: the int32 entry points'
+// kernels then come out of the compiler in the order, and so under the labels, they always had
+// (scripts/asm_digest.py compares them with the parent's).
+static void launch_pack_keys(int kc, unsigned grid, hipStream_t s, const int32_t *keys_in, const uint32_t *vals_in,
+                             uint64_t *packed, uint64_t n, uint32_t base);
+static void launch_unpack_keys(int kc, unsigned grid, hipStream_t s, const uint64_t *packed, int32_t *keys_out,
+                               uint32_t *vals_out, uint64_t n);
+
 static int pack(dsort_ctx *ctx, const int32_t *keys_in, const uint32_t *vals_in, uint64_t *packed, size_t n,
-                uint32_t base, hipStream_t s) {
+                uint32_t base, hipStream_t s, int kc = 0) {
     const unsigned grid = grid_for((n + 3) / 4);
-    if (vals_in)
+    if (kc)
+        launch_pack_keys(kc, grid, s, keys_in, vals_in, packed, (uint64_t)n, base);
+    else if (vals_in)
         hipLaunchKernelGGL((pairs_pack_kernel<false>), dim3(grid), dim3(NT), 0, s, keys_in, vals_in, packed,
                            (uint64_t)n, base);
     else
@@ -169,9 +238,11 @@ static int pack(dsort_ctx *ctx, const int32_t *keys_in, const uint32_t *vals_in,
 
 // Sorts (keys_in[i], vals_in ? vals_in[i] : i) by key, then by value as unsigned 32-bit, into
 // keys_out / vals_out (either may be NULL: not wanted; either may be its input: the pack has
-// consumed the inputs before the unpack writes).  Asynchronous on s.
-static int pairs_sort(dsort_ctx *ctx, const int32_t *keys_in, const uint32_t *vals_in, int32_t *keys_out,
-                      uint32_t *vals_out, size_t n, hipStream_t s) {
+// consumed the inputs before the unpack writes).  Asynchronous on s.  kc: the key codec
+// (dsort_keycodec.h; 0 = int32 ascending, the kernels of the int32 entry points), under which
+// "key" is the typed key and its order the codec's.
+int pairs_sort(dsort_ctx *ctx, const int32_t *keys_in, const uint32_t *vals_in, int32_t *keys_out,
+               uint32_t *vals_out, size_t n, hipStream_t s, int kc) {
     if (n == 0) {
         ctx->stats = fresh_stats();
         ctx->ev_mask = 0;
@@ -188,7 +259,7 @@ static int pairs_sort(dsort_ctx *ctx, const int32_t *keys_in, const uint32_t *va
     uint64_t *packed = static_cast<uint64_t *>(ctx->pairs);
     ctx->pairs_ev_ok = leg_event(ctx, 0, s);
     const unsigned grid = grid_for((n + 3) / 4);
-    rc = pack(ctx, keys_in, vals_in, packed, n, 0, s);
+    rc = pack(ctx, keys_in, vals_in, packed, n, 0, s, kc);
     if (rc) return rc;
     ctx->pairs_ev_ok = ctx->pairs_ev_ok && leg_event(ctx, 1, s);
     // DSORT_OPT_KILL_AFTER_STAGE fires inside, as for any int64 sort of n keys; DSORT_ESTAGE (the
@@ -197,7 +268,10 @@ static int pairs_sort(dsort_ctx *ctx, const int32_t *keys_in, const uint32_t *va
                                          n, s, true);
     if (src && src != DSORT_ESTAGE) return src;
     ctx->pairs_ev_ok = ctx->pairs_ev_ok && leg_event(ctx, 2, s);
-    hipLaunchKernelGGL(pairs_unpack_kernel, dim3(grid), dim3(NT), 0, s, packed, keys_out, vals_out, (uint64_t)n);
+    if (kc)
+        launch_unpack_keys(kc, grid, s, packed, keys_out, vals_out, (uint64_t)n);
+    else
+        hipLaunchKernelGGL(pairs_unpack_kernel, dim3(grid), dim3(NT), 0, s, packed, keys_out, vals_out, (uint64_t)n);
     DSORT_HIP(ctx, hipGetLastError());
     ctx->pairs_ev_ok = ctx->pairs_ev_ok && leg_event(ctx, 3, s);
     rc = order_end(ctx, s);
@@ -360,3 +434,26 @@ int dsort_pairs_leg_ms(dsort_ctx *ctx, double ms[3]) {
 }
 
 }  // extern "C"
+
+namespace dsort {
+namespace pr {
+
+static void launch_pack_keys(int kc, unsigned grid, hipStream_t s, const int32_t *keys_in, const uint32_t *vals_in,
+                             uint64_t *packed, uint64_t n, uint32_t base) {
+    if (vals_in) {
+        DSORT_KC_SWITCH(kc, hipLaunchKernelGGL((pairs_pack_keys_kernel<false, KC_>), dim3(grid), dim3(NT), 0, s,
+                                               keys_in, vals_in, packed, n, base));
+    } else {
+        DSORT_KC_SWITCH(kc, hipLaunchKernelGGL((pairs_pack_keys_kernel<true, KC_>), dim3(grid), dim3(NT), 0, s,
+                                               keys_in, vals_in, packed, n, base));
+    }
+}
+
+static void launch_unpack_keys(int kc, unsigned grid, hipStream_t s, const uint64_t *packed, int32_t *keys_out,
+                               uint32_t *vals_out, uint64_t n) {
+    DSORT_KC_SWITCH(kc, hipLaunchKernelGGL((pairs_unpack_keys_kernel<KC_>), dim3(grid), dim3(NT), 0, s, packed,
+                                           keys_out, vals_out, n));
+}
+
+}  // namespace pr
+}  // namespace dsort

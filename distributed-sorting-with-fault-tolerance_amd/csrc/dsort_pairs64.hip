@@ -43,6 +43,7 @@
 
 #include "dsort_exch.h"
 #include "dsort_internal.h"
+#include "dsort_keycodec.h"
 
 namespace dsort {
 namespace p64 {
@@ -91,8 +92,48 @@ __device__ __forceinline__ void block_minmax(int64_t &lo, int64_t &hi) {
     }
 }
 
-// part[2 g], part[2 g + 1] = min, max of the keys workgroup g saw (grid-stride, 16-byte loads, two
-// in flight per lane)
+// Every kernel below that reads the caller's keys or writes them back exists twice: the one the
+// int64 entry points have always launched, under its name and with its machine code, and a
+// *_keys_kernel that takes the key codec KC (dsort_keycodec.h) as a template parameter, for the typed
+// entry points (dsort_keys.hip): keys are encoded as they are read and decoded as they are
+// written, and everything in between works on the encoded words.  regroup64 and final64 are one
+// body behind both kernels (the identity codec compiles to the old code); minmax, pack64 and
+// unpack64 keep the old kernel's text beside the templated one.
+
+// part[2 g], part[2 g + 1] = min, max of the (encoded) keys workgroup g saw (grid-stride, 16-byte
+// loads, two in flight per lane)
+template <int KC>
+__global__ void __launch_bounds__(NT) minmax_keys_kernel(const int64_t *__restrict__ keys, uint64_t n,
+                                                         int64_t *__restrict__ part) {
+    int64_t lo = INT64_MAX, hi = INT64_MIN;
+    const uint64_t groups = n >> 1;
+    const uint64_t stride = (uint64_t)gridDim.x * NT;
+    const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
+    auto take = [&](uint64_t v) {
+        const int64_t k = (int64_t)kc::Codec<KC>::enc(v);
+        lo = k < lo ? k : lo;
+        hi = k > hi ? k : hi;
+    };
+    uint64_t g = t;
+    for (; g + stride < groups; g += 2 * stride) {
+        const k2_a8 a = *reinterpret_cast<const k2_a8 *>(keys + 2 * g);
+        const k2_a8 b = *reinterpret_cast<const k2_a8 *>(keys + 2 * (g + stride));
+        take(a.x), take(a.y), take(b.x), take(b.y);
+    }
+    if (g < groups) {
+        const k2_a8 a = *reinterpret_cast<const k2_a8 *>(keys + 2 * g);
+        take(a.x), take(a.y);
+    }
+    if (t == 0 && (n & 1)) take((uint64_t)keys[n - 1]);
+    block_minmax(lo, hi);
+    if (threadIdx.x == 0) {
+        part[2 * blockIdx.x] = lo;
+        part[2 * blockIdx.x + 1] = hi;
+    }
+}
+// The same without a codec: the kernel of the int64 entry points, kept word for word.  (As one body
+// shared with the kernel above, its instructions came out of the compiler in a slightly different
+// order; scripts/asm_digest.py compares it with the parent's.)
 __global__ void __launch_bounds__(NT) minmax_kernel(const int64_t *__restrict__ keys, uint64_t n,
                                                     int64_t *__restrict__ part) {
     int64_t lo = INT64_MAX, hi = INT64_MIN;
@@ -147,6 +188,33 @@ __device__ __forceinline__ uint64_t pack_word(uint64_t key, uint64_t i, uint64_t
 
 // `base` = the global position of keys[0] (a sample argsort; 0 in a local one): element i packs the
 // position base + i.
+template <bool WIDE, int KC>
+__global__ void __launch_bounds__(NT) pack64_keys_kernel(const int64_t *__restrict__ keys,
+                                                         uint64_t *__restrict__ packed, uint64_t n, uint64_t kmin,
+                                                         int b, uint64_t base) {
+    using C = kc::Codec<KC>;
+    const uint64_t chunks = n >> 8;
+    const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * NT) >> 6;
+    const uint32_t l = threadIdx.x & 63;
+    for (uint64_t c = t >> 6; c < chunks; c += nwaves) {
+        const uint64_t e0 = (c << 8) + 2 * l, e1 = e0 + 128;
+        const uint64_t p0 = base + e0, p1 = base + e1;
+        const k2_a8 k0 = *reinterpret_cast<const k2_a8 *>(keys + e0);
+        const k2_a8 k1 = *reinterpret_cast<const k2_a8 *>(keys + e1);
+        __builtin_nontemporal_store(
+            l2{pack_word<WIDE>(C::enc(k0.x), p0, kmin, b), pack_word<WIDE>(C::enc(k0.y), p0 + 1, kmin, b)},
+            reinterpret_cast<l2 *>(packed + e0));
+        __builtin_nontemporal_store(
+            l2{pack_word<WIDE>(C::enc(k1.x), p1, kmin, b), pack_word<WIDE>(C::enc(k1.y), p1 + 1, kmin, b)},
+            reinterpret_cast<l2 *>(packed + e1));
+    }
+    const uint64_t i = (chunks << 8) + t;  // the n % 256 last elements, one each
+    if (i < n) packed[i] = pack_word<WIDE>(C::enc((uint64_t)keys[i]), base + i, kmin, b);
+}
+// The same without a codec: the kernel of the int64 entry points, kept word for word.  (As one body
+// shared with the kernel above, its instructions came out of the compiler in a slightly different
+// order; scripts/asm_digest.py compares it with the parent's.)
 template <bool WIDE>
 __global__ void __launch_bounds__(NT) pack64_kernel(const int64_t *__restrict__ keys, uint64_t *__restrict__ packed,
                                                     uint64_t n, uint64_t kmin, int b, uint64_t base) {
@@ -172,6 +240,45 @@ __global__ void __launch_bounds__(NT) pack64_kernel(const int64_t *__restrict__ 
 
 // ------------------------------------------------------------------ narrow unpack --------
 // idx_out[i] = the low b bits of u = packed[i] ^ SIGN, keys_out[i] (NULL: not wanted) = (u >> b) + min
+// (the encoded word, which the codec turns back into the caller's key)
+template <int KC>
+__global__ void __launch_bounds__(NT) unpack64_keys_kernel(const uint64_t *__restrict__ packed,
+                                                           int64_t *__restrict__ keys_out,
+                                                           uint32_t *__restrict__ idx_out, uint64_t n, uint64_t kmin,
+                                                           int b) {
+    using C = kc::Codec<KC>;
+    const uint64_t mask = (1ull << b) - 1;
+    const uint64_t chunks = n >> 8;
+    const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
+    const uint64_t nwaves = ((uint64_t)gridDim.x * NT) >> 6;
+    const uint32_t l = threadIdx.x & 63;
+    for (uint64_t c = t >> 6; c < chunks; c += nwaves) {
+        const uint64_t e0 = (c << 8) + 2 * l, e1 = e0 + 128;
+        l2 a = *reinterpret_cast<const l2 *>(packed + e0);
+        l2 d = *reinterpret_cast<const l2 *>(packed + e1);
+        a ^= SIGN;
+        d ^= SIGN;
+        __builtin_nontemporal_store(u2_a4{(uint32_t)(a.x & mask), (uint32_t)(a.y & mask)},
+                                    reinterpret_cast<u2_a4 *>(idx_out + e0));
+        __builtin_nontemporal_store(u2_a4{(uint32_t)(d.x & mask), (uint32_t)(d.y & mask)},
+                                    reinterpret_cast<u2_a4 *>(idx_out + e1));
+        if (keys_out) {
+            __builtin_nontemporal_store(k2_a8{C::dec((a.x >> b) + kmin), C::dec((a.y >> b) + kmin)},
+                                        reinterpret_cast<k2_a8 *>(keys_out + e0));
+            __builtin_nontemporal_store(k2_a8{C::dec((d.x >> b) + kmin), C::dec((d.y >> b) + kmin)},
+                                        reinterpret_cast<k2_a8 *>(keys_out + e1));
+        }
+    }
+    const uint64_t i = (chunks << 8) + t;
+    if (i < n) {
+        const uint64_t u = packed[i] ^ SIGN;
+        idx_out[i] = (uint32_t)(u & mask);
+        if (keys_out) keys_out[i] = (int64_t)C::dec((u >> b) + kmin);
+    }
+}
+// The same without a codec: the kernel of the int64 entry points, kept word for word.  (As one body
+// shared with the kernel above, its instructions came out of the compiler in a slightly different
+// order; scripts/asm_digest.py compares it with the parent's.)
 __global__ void __launch_bounds__(NT) unpack64_kernel(const uint64_t *__restrict__ packed, int64_t *__restrict__ keys_out,
                                                       uint32_t *__restrict__ idx_out, uint64_t n, uint64_t kmin,
                                                       int b) {
@@ -206,9 +313,11 @@ __global__ void __launch_bounds__(NT) unpack64_kernel(const uint64_t *__restrict
 }
 
 // ------------------------------------------------------------------ wide: regroup --------
-// B[j] = hi32(keys[p]) : j, p = the low word of A[j] (A sorted by the low halves)
-__global__ void __launch_bounds__(NT) regroup64_kernel(const uint64_t *__restrict__ A, const int64_t *__restrict__ keys,
-                                                       uint64_t *__restrict__ B, uint64_t n) {
+// B[j] = hi32(enc(keys[p])) : j, p = the low word of A[j] (A sorted by the low halves): the keys are
+// the caller's, read at random, so each is encoded again before its high half is taken
+template <int KC>
+__device__ __forceinline__ void regroup64_body(const uint64_t *A, const int64_t *keys, uint64_t *B, uint64_t n) {
+    using C = kc::Codec<KC>;
     const uint64_t chunks = n >> 8;
     const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
     const uint64_t nwaves = ((uint64_t)gridDim.x * NT) >> 6;
@@ -218,8 +327,8 @@ __global__ void __launch_bounds__(NT) regroup64_kernel(const uint64_t *__restric
         const l2 a = *reinterpret_cast<const l2 *>(A + e0);
         const l2 d = *reinterpret_cast<const l2 *>(A + e1);
         // four independent random reads in flight
-        const uint64_t k0 = (uint64_t)keys[(uint32_t)a.x], k1 = (uint64_t)keys[(uint32_t)a.y];
-        const uint64_t k2 = (uint64_t)keys[(uint32_t)d.x], k3 = (uint64_t)keys[(uint32_t)d.y];
+        const uint64_t k0 = C::enc((uint64_t)keys[(uint32_t)a.x]), k1 = C::enc((uint64_t)keys[(uint32_t)a.y]);
+        const uint64_t k2 = C::enc((uint64_t)keys[(uint32_t)d.x]), k3 = C::enc((uint64_t)keys[(uint32_t)d.y]);
         __builtin_nontemporal_store(
             l2{word((uint32_t)(k0 >> 32), (uint32_t)e0), word((uint32_t)(k1 >> 32), (uint32_t)e0 + 1)},
             reinterpret_cast<l2 *>(B + e0));
@@ -228,20 +337,32 @@ __global__ void __launch_bounds__(NT) regroup64_kernel(const uint64_t *__restric
             reinterpret_cast<l2 *>(B + e1));
     }
     const uint64_t i = (chunks << 8) + t;
-    if (i < n) B[i] = word((uint32_t)((uint64_t)keys[(uint32_t)A[i]] >> 32), (uint32_t)i);
+    if (i < n) B[i] = word((uint32_t)(C::enc((uint64_t)keys[(uint32_t)A[i]]) >> 32), (uint32_t)i);
+}
+__global__ void __launch_bounds__(NT) regroup64_kernel(const uint64_t *__restrict__ A, const int64_t *__restrict__ keys,
+                                                       uint64_t *__restrict__ B, uint64_t n) {
+    regroup64_body<0>(A, keys, B, n);
+}
+template <int KC>
+__global__ void __launch_bounds__(NT) regroup64_keys_kernel(const uint64_t *__restrict__ A,
+                                                            const int64_t *__restrict__ keys,
+                                                            uint64_t *__restrict__ B, uint64_t n) {
+    regroup64_body<KC>(A, keys, B, n);
 }
 
 // ------------------------------------------------------------------ wide: final ----------
 // r -> j = the low word of B[r] (B sorted by the high halves), A[j] = (lo ^ BIAS) : p:
-// idx_out[r] = p, keys_out[r] (NULL: not wanted) = hi32 : lo
-__global__ void __launch_bounds__(NT) final64_kernel(const uint64_t *__restrict__ B, const uint64_t *__restrict__ A,
-                                                     int64_t *__restrict__ keys_out, uint32_t *__restrict__ idx_out,
-                                                     uint64_t n) {
+// idx_out[r] = p, keys_out[r] (NULL: not wanted) = the codec's decoding of hi32 : lo
+template <int KC>
+__device__ __forceinline__ void final64_body(const uint64_t *B, const uint64_t *A, int64_t *keys_out,
+                                             uint32_t *idx_out, uint64_t n) {
     const uint64_t chunks = n >> 8;
     const uint64_t t = (uint64_t)blockIdx.x * NT + threadIdx.x;
     const uint64_t nwaves = ((uint64_t)gridDim.x * NT) >> 6;
     const uint32_t l = threadIdx.x & 63;
-    auto key_of = [](uint64_t bw, uint64_t aw) { return word((uint32_t)(bw >> 32), (uint32_t)(aw >> 32) ^ BIAS); };
+    auto key_of = [](uint64_t bw, uint64_t aw) {
+        return kc::Codec<KC>::dec(word((uint32_t)(bw >> 32), (uint32_t)(aw >> 32) ^ BIAS));
+    };
     for (uint64_t c = t >> 6; c < chunks; c += nwaves) {
         const uint64_t e0 = (c << 8) + 2 * l, e1 = e0 + 128;
         const l2 x = *reinterpret_cast<const l2 *>(B + e0);
@@ -264,6 +385,18 @@ __global__ void __launch_bounds__(NT) final64_kernel(const uint64_t *__restrict_
         idx_out[i] = (uint32_t)aw;
         if (keys_out) keys_out[i] = (int64_t)key_of(bw, aw);
     }
+}
+__global__ void __launch_bounds__(NT) final64_kernel(const uint64_t *__restrict__ B, const uint64_t *__restrict__ A,
+                                                     int64_t *__restrict__ keys_out, uint32_t *__restrict__ idx_out,
+                                                     uint64_t n) {
+    final64_body<0>(B, A, keys_out, idx_out, n);
+}
+template <int KC>
+__global__ void __launch_bounds__(NT) final64_keys_kernel(const uint64_t *__restrict__ B,
+                                                          const uint64_t *__restrict__ A,
+                                                          int64_t *__restrict__ keys_out,
+                                                          uint32_t *__restrict__ idx_out, uint64_t n) {
+    final64_body<KC>(B, A, keys_out, idx_out, n);
 }
 
 // ------------------------------------------------------------------ across ranks ---------
@@ -354,6 +487,19 @@ __global__ void __launch_bounds__(NT) final_stream64_kernel(const uint64_t *__re
 }
 
 // ------------------------------------------------------------------ host -----------------
+// The launches of the typed kernels, defined at the end of the file: the int64 entry points'
+// kernels then come out of the compiler in the order, and so under the labels, they always had
+// (scripts/asm_digest.py compares them with the parent's).
+static void launch_minmax_keys(int kc, unsigned grid, hipStream_t s, const int64_t *keys, uint64_t n, int64_t *part);
+static void launch_pack64_keys(int kc, bool wide, unsigned grid, hipStream_t s, const int64_t *keys, uint64_t *packed,
+                               uint64_t n, uint64_t kmin, int b, uint64_t base);
+static void launch_unpack64_keys(int kc, unsigned grid, hipStream_t s, const uint64_t *packed, int64_t *keys_out,
+                                 uint32_t *idx_out, uint64_t n, uint64_t kmin, int b);
+static void launch_regroup64_keys(int kc, unsigned grid, hipStream_t s, const uint64_t *A, const int64_t *keys,
+                                  uint64_t *B, uint64_t n);
+static void launch_final64_keys(int kc, unsigned grid, hipStream_t s, const uint64_t *B, const uint64_t *A,
+                                int64_t *keys_out, uint32_t *idx_out, uint64_t n);
+
 static unsigned grid_for(uint64_t lanes) {
     const uint64_t g = (lanes + NT - 1) / NT;
     return (unsigned)(g > MAXWG ? MAXWG : (g ? g : 1));
@@ -380,7 +526,8 @@ static void leg_event(dsort_ctx *ctx, hipStream_t s) {
 
 // min and max of keys[0..n), n > 0, on the host: two launches, a 16-byte copy into the pinned
 // mirror and one host wait.
-static int minmax(dsort_ctx *ctx, const int64_t *keys, size_t n, hipStream_t s, int64_t *kmin, int64_t *kmax) {
+static int minmax(dsort_ctx *ctx, const int64_t *keys, size_t n, hipStream_t s, int64_t *kmin, int64_t *kmax,
+                  int kc = 0) {
     int rc = ensure(ctx, &ctx->a64_part, &ctx->a64_part_bytes, (size_t)(MAXWG + 1) * 16, "argsort min/max partials");
     if (rc) return rc;
     if ((rc = ensure_small_host(ctx, 16))) return rc;
@@ -388,7 +535,11 @@ static int minmax(dsort_ctx *ctx, const int64_t *keys, size_t n, hipStream_t s, 
         return set_err(ctx, DSORT_EHIP, "hipEventCreate");
     int64_t *part = static_cast<int64_t *>(ctx->a64_part);
     const unsigned grid = grid_for(((uint64_t)n + 3) / 4);
-    hipLaunchKernelGGL(minmax_kernel, dim3(grid), dim3(NT), 0, s, keys, (uint64_t)n, part);
+    if (kc) {
+        launch_minmax_keys(kc, grid, s, keys, (uint64_t)n, part);
+    } else {
+        hipLaunchKernelGGL(minmax_kernel, dim3(grid), dim3(NT), 0, s, keys, (uint64_t)n, part);
+    }
     DSORT_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(minmax_final_kernel, dim3(1), dim3(NT), 0, s, part, (uint32_t)grid, part + 2 * MAXWG);
     DSORT_HIP(ctx, hipGetLastError());
@@ -416,8 +567,10 @@ static int inner_sort(dsort_ctx *ctx, uint64_t *words, size_t n, hipStream_t s, 
 // d_idx_out[j] = the position in keys of the j-th smallest key, equal keys in input order;
 // keys_out (NULL: not wanted; may be keys: the pack / the regroup has consumed the keys before the
 // last kernel writes).  Asynchronous on s but for the min/max read-back of the automatic mode.
-static int argsort64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uint32_t *idx_out, size_t n,
-                     hipStream_t s) {
+// kc: the key codec (dsort_keycodec.h; 0 = int64 ascending, the kernels of the int64 entry points):
+// min, max and the plan are those of the ENCODED words, whose signed order is the typed keys' order.
+int argsort64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uint32_t *idx_out, size_t n, hipStream_t s,
+              int kc) {
     if (n == 0) {
         ctx->stats = fresh_stats();
         ctx->ev_mask = 0;
@@ -437,7 +590,7 @@ static int argsort64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uin
     int64_t kmin = 0, kmax = 0;
     leg_event(ctx, s);
     if (!ctx->opt.argsort_wide) {
-        if ((rc = minmax(ctx, keys, n, s, &kmin, &kmax))) return rc;
+        if ((rc = minmax(ctx, keys, n, s, &kmin, &kmax, kc))) return rc;
         if ((rc = plan_argsort64(n, kmin, kmax, &b, &passes)))
             return set_err(ctx, DSORT_EHIP, "argsort: the min/max reduction returned min > max");
         ctx->a64_minmax = true;
@@ -446,35 +599,55 @@ static int argsort64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uin
     const unsigned grid = grid_for(((uint64_t)n + 3) / 4);
     int done = 0, src;
     if (passes == 1) {
-        hipLaunchKernelGGL((pack64_kernel<false>), dim3(grid), dim3(NT), 0, s, keys, A, (uint64_t)n, (uint64_t)kmin, b,
-                           (uint64_t)0);
+        if (kc) {
+            launch_pack64_keys(kc, false, grid, s, keys, A, (uint64_t)n, (uint64_t)kmin, b, (uint64_t)0);
+        } else {
+            hipLaunchKernelGGL((pack64_kernel<false>), dim3(grid), dim3(NT), 0, s, keys, A, (uint64_t)n, (uint64_t)kmin,
+                               b, (uint64_t)0);
+        }
         DSORT_HIP(ctx, hipGetLastError());
         leg_event(ctx, s);
         // DSORT_ESTAGE (the kill stage was never reached) leaves a valid output: the rest still runs
         src = inner_sort(ctx, A, n, s, &done);
         if (src && src != DSORT_ESTAGE) return src;
         leg_event(ctx, s);
-        hipLaunchKernelGGL(unpack64_kernel, dim3(grid), dim3(NT), 0, s, A, keys_out, idx_out, (uint64_t)n,
-                           (uint64_t)kmin, b);
+        if (kc) {
+            launch_unpack64_keys(kc, grid, s, A, keys_out, idx_out, (uint64_t)n, (uint64_t)kmin, b);
+        } else {
+            hipLaunchKernelGGL(unpack64_kernel, dim3(grid), dim3(NT), 0, s, A, keys_out, idx_out, (uint64_t)n,
+                               (uint64_t)kmin, b);
+        }
         DSORT_HIP(ctx, hipGetLastError());
     } else {
         rc = ensure(ctx, &ctx->a64_b, &ctx->a64_b_bytes, n * 8, "argsort second arena");
         if (rc) return rc;
         uint64_t *B = static_cast<uint64_t *>(ctx->a64_b);
-        hipLaunchKernelGGL((pack64_kernel<true>), dim3(grid), dim3(NT), 0, s, keys, A, (uint64_t)n, (uint64_t)0, 0,
-                           (uint64_t)0);
+        if (kc) {
+            launch_pack64_keys(kc, true, grid, s, keys, A, (uint64_t)n, (uint64_t)0, 0, (uint64_t)0);
+        } else {
+            hipLaunchKernelGGL((pack64_kernel<true>), dim3(grid), dim3(NT), 0, s, keys, A, (uint64_t)n, (uint64_t)0, 0,
+                               (uint64_t)0);
+        }
         DSORT_HIP(ctx, hipGetLastError());
         leg_event(ctx, s);
         src = inner_sort(ctx, A, n, s, &done);
         if (src && src != DSORT_ESTAGE) return src;
         leg_event(ctx, s);
-        hipLaunchKernelGGL(regroup64_kernel, dim3(grid), dim3(NT), 0, s, A, keys, B, (uint64_t)n);
+        if (kc) {
+            launch_regroup64_keys(kc, grid, s, A, keys, B, (uint64_t)n);
+        } else {
+            hipLaunchKernelGGL(regroup64_kernel, dim3(grid), dim3(NT), 0, s, A, keys, B, (uint64_t)n);
+        }
         DSORT_HIP(ctx, hipGetLastError());
         leg_event(ctx, s);
         src = inner_sort(ctx, B, n, s, &done);
         if (src && src != DSORT_ESTAGE) return src;
         leg_event(ctx, s);
-        hipLaunchKernelGGL(final64_kernel, dim3(grid), dim3(NT), 0, s, B, A, keys_out, idx_out, (uint64_t)n);
+        if (kc) {
+            launch_final64_keys(kc, grid, s, B, A, keys_out, idx_out, (uint64_t)n);
+        } else {
+            hipLaunchKernelGGL(final64_kernel, dim3(grid), dim3(NT), 0, s, B, A, keys_out, idx_out, (uint64_t)n);
+        }
         DSORT_HIP(ctx, hipGetLastError());
     }
     leg_event(ctx, s);
@@ -900,3 +1073,41 @@ int dsort_sample_argsort64_leg_ms(dsort_ctx *ctx, double ms[10], int *legs) {
 }
 
 }  // extern "C"
+
+namespace dsort {
+namespace p64 {
+
+static void launch_minmax_keys(int kc, unsigned grid, hipStream_t s, const int64_t *keys, uint64_t n, int64_t *part) {
+    DSORT_KC_SWITCH(kc, hipLaunchKernelGGL((minmax_keys_kernel<KC_>), dim3(grid), dim3(NT), 0, s, keys, n, part));
+}
+
+static void launch_pack64_keys(int kc, bool wide, unsigned grid, hipStream_t s, const int64_t *keys, uint64_t *packed,
+                               uint64_t n, uint64_t kmin, int b, uint64_t base) {
+    if (wide) {
+        DSORT_KC_SWITCH(kc, hipLaunchKernelGGL((pack64_keys_kernel<true, KC_>), dim3(grid), dim3(NT), 0, s, keys, packed,
+                                               n, kmin, b, base));
+    } else {
+        DSORT_KC_SWITCH(kc, hipLaunchKernelGGL((pack64_keys_kernel<false, KC_>), dim3(grid), dim3(NT), 0, s, keys,
+                                               packed, n, kmin, b, base));
+    }
+}
+
+static void launch_unpack64_keys(int kc, unsigned grid, hipStream_t s, const uint64_t *packed, int64_t *keys_out,
+                                 uint32_t *idx_out, uint64_t n, uint64_t kmin, int b) {
+    DSORT_KC_SWITCH(kc, hipLaunchKernelGGL((unpack64_keys_kernel<KC_>), dim3(grid), dim3(NT), 0, s, packed, keys_out,
+                                           idx_out, n, kmin, b));
+}
+
+static void launch_regroup64_keys(int kc, unsigned grid, hipStream_t s, const uint64_t *A, const int64_t *keys,
+                                  uint64_t *B, uint64_t n) {
+    DSORT_KC_SWITCH(kc, hipLaunchKernelGGL((regroup64_keys_kernel<KC_>), dim3(grid), dim3(NT), 0, s, A, keys, B, n));
+}
+
+static void launch_final64_keys(int kc, unsigned grid, hipStream_t s, const uint64_t *B, const uint64_t *A,
+                                int64_t *keys_out, uint32_t *idx_out, uint64_t n) {
+    DSORT_KC_SWITCH(kc, hipLaunchKernelGGL((final64_keys_kernel<KC_>), dim3(grid), dim3(NT), 0, s, B, A, keys_out,
+                                           idx_out, n));
+}
+
+}  // namespace p64
+}  // namespace dsort

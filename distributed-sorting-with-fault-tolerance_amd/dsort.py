@@ -48,7 +48,18 @@ EXPORTS = [
     "dsort_sample_gather_dev", "dsort_plan_gather_table", "dsort_plan_gather_route",
     "dsort_argsort_dev_i64", "dsort_argsort_i64", "dsort_sort_records_dev_i64", "dsort_plan_argsort_i64",
     "dsort_sample_argsort_dev_i64", "dsort_plan_sample_argsort_i64",
+    # typed keys and descending order (an ABI 10 addition)
+    "dsort_key_encode", "dsort_key_decode", "dsort_sort_dev_keys", "dsort_sort_dev_copy_keys",
+    "dsort_sort_keys", "dsort_argsort_dev_keys", "dsort_argsort_keys", "dsort_sort_pairs_dev_keys",
+    "dsort_sort_records_dev_keys", "dsort_sample_sort_dev_keys", "dsort_sample_argsort_dev_keys",
 ]
+
+# DSORT_KEY_* and DSORT_ORDER_DESCENDING (include/dsort.h, "Key types and order")
+KEY_TYPES = {"i32": 0, "u32": 1, "f32": 2, "i64": 3, "u64": 4, "f64": 5}
+ORDER_DESCENDING = 1
+_KEY_OF_NP = {np.dtype(np.int32): "i32", np.dtype(np.uint32): "u32", np.dtype(np.float32): "f32",
+              np.dtype(np.int64): "i64", np.dtype(np.uint64): "u64", np.dtype(np.float64): "f64"}
+_NP_OF_KEY = {v: k for k, v in _KEY_OF_NP.items()}
 
 
 # dsort_set_option / dsort_get_option (include/dsort.h)
@@ -282,6 +293,20 @@ def load():
                                                         ctypes.POINTER(SZ), P]),
         "dsort_plan_sample_argsort_i64": (ctypes.c_int, [ctypes.c_int, P, P, P, P, ctypes.POINTER(ctypes.c_int),
                                                          ctypes.POINTER(ctypes.c_int)]),
+        "dsort_key_encode": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, P, P, SZ]),
+        "dsort_key_decode": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, P, P, SZ]),
+        "dsort_sort_dev_keys": (ctypes.c_int, [P, P, SZ, ctypes.c_int, ctypes.c_int, P]),
+        "dsort_sort_dev_copy_keys": (ctypes.c_int, [P, P, P, SZ, ctypes.c_int, ctypes.c_int, P]),
+        "dsort_sort_keys": (ctypes.c_int, [P, P, SZ, ctypes.c_int, ctypes.c_int]),
+        "dsort_argsort_dev_keys": (ctypes.c_int, [P, P, P, P, SZ, ctypes.c_int, ctypes.c_int, P]),
+        "dsort_argsort_keys": (ctypes.c_int, [P, P, P, P, SZ, ctypes.c_int, ctypes.c_int]),
+        "dsort_sort_pairs_dev_keys": (ctypes.c_int, [P, P, P, P, P, SZ, ctypes.c_int, ctypes.c_int, P]),
+        "dsort_sort_records_dev_keys": (ctypes.c_int, [P, P, P, P, P, SZ, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                       P]),
+        "dsort_sample_sort_dev_keys": (ctypes.c_int, [P, P, SZ, ctypes.c_int, ctypes.c_int, ctypes.POINTER(P),
+                                                      ctypes.POINTER(SZ), P]),
+        "dsort_sample_argsort_dev_keys": (ctypes.c_int, [P, P, SZ, U64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(P),
+                                                         ctypes.POINTER(P), ctypes.POINTER(SZ), P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -302,6 +327,47 @@ def _sfx(dtype):
     if dt == np.int64:
         return "i64"
     raise DsortError(f"unsupported key type {dt} (int32 / int64)")
+
+
+def _key_name(dtype_name, itemsize, key_type):
+    """The key type name ("f32", ...) of an array or tensor: its own dtype's, or the `key_type`
+    override, whose width must be the element size (an int32 array sorted as "u32")."""
+    if key_type is None:
+        if dtype_name is None:
+            raise DsortError("unsupported key dtype (float32/float64/uint32/uint64/int32/int64)")
+        return dtype_name
+    if key_type not in KEY_TYPES:
+        raise DsortError(f"unknown key_type {key_type!r} (one of {', '.join(KEY_TYPES)})")
+    if int(key_type[1:]) != 8 * itemsize:
+        raise DsortError(f"key_type {key_type!r} does not match the {itemsize}-byte elements")
+    return key_type
+
+
+def _np_key(a, key_type):
+    return _key_name(_KEY_OF_NP.get(a.dtype), a.dtype.itemsize, key_type)
+
+
+def key_encode(keys, descending=False, key_type=None):
+    """The order-preserving words of a numpy key array (dsort_key_encode, the rule the kernels run):
+    a new signed-integer array of the keys' width whose signed order is the keys' order (float:
+    IEEE totalOrder), reversed with descending=True."""
+    keys = np.ascontiguousarray(keys)
+    name = _np_key(keys, key_type)
+    words = np.empty(keys.shape, np.int32 if keys.dtype.itemsize == 4 else np.int64)
+    _check(None, load().dsort_key_encode(KEY_TYPES[name], ORDER_DESCENDING if descending else 0, _ptr(keys),
+                                         _ptr(words), keys.size))
+    return words
+
+
+def key_decode(words, key_type, descending=False):
+    """The keys of the words key_encode made (dsort_key_decode): a new array of the numpy type of
+    `key_type` ("f32", "u64", ...), bit-exact."""
+    words = np.ascontiguousarray(words)
+    name = _key_name(None, words.dtype.itemsize, key_type)
+    keys = np.empty(words.shape, _NP_OF_KEY[name])
+    _check(None, load().dsort_key_decode(KEY_TYPES[name], ORDER_DESCENDING if descending else 0, _ptr(words),
+                                         _ptr(keys), words.size))
+    return keys
 
 
 # ----------------------------------------------------------------- host-only planning helpers
@@ -474,11 +540,17 @@ class Context:
         return m.value
 
     # ---------------- host-buffer entry points (reference drop-ins) ----------------------
-    def sort(self, keys):
-        """In-place sort of a host numpy int32/int64 array (dsort_sort_*)."""
+    def sort(self, keys, descending=False, key_type=None):
+        """In-place sort of a host numpy array (dsort_sort_i32 / _i64; any other key type, a
+        `key_type` override or descending=True: dsort_sort_keys)."""
         assert keys.flags.c_contiguous
-        f = getattr(self.lib, f"dsort_sort_{_sfx(keys.dtype)}")
-        self.check(f(self.h, _ptr(keys), keys.size))
+        name = _np_key(keys, key_type)
+        if name in ("i32", "i64") and not descending:
+            f = getattr(self.lib, f"dsort_sort_{name}")
+            self.check(f(self.h, _ptr(keys), keys.size))
+        else:
+            self.check(self.lib.dsort_sort_keys(self.h, _ptr(keys), keys.size, KEY_TYPES[name],
+                                                ORDER_DESCENDING if descending else 0))
         return keys
 
     def merge(self, runs):
@@ -509,9 +581,40 @@ class Context:
             return "i64"
         raise DsortError(f"unsupported tensor dtype {t.dtype}")
 
-    def sort_dev(self, t, out=None):
-        """Sort a CUDA tensor in place, or into `out` (dsort_sort_dev[_copy]_*)."""
-        sfx = self._tsfx(t)
+    @staticmethod
+    def _tkey(t, key_type=None, descending=False):
+        """(name, typed) of a key tensor: its key type name and whether the call goes to the *_keys
+        entry points (anything but signed integers ascending)."""
+        names = {torch.int32: "i32", torch.float32: "f32", torch.int64: "i64", torch.float64: "f64"}
+        for dt, nm in (("uint32", "u32"), ("uint64", "u64")):
+            if hasattr(torch, dt):
+                names[getattr(torch, dt)] = nm
+        name = _key_name(names.get(t.dtype), t.element_size(), key_type)
+        return name, bool(descending) or name not in ("i32", "i64")
+
+    @staticmethod
+    def _keys1d(t, what, n=None, like=None):
+        if not t.is_contiguous() or t.dim() != 1 or (like is not None and t.dtype != like.dtype):
+            raise DsortError(f"{what}: a contiguous 1-d tensor of the keys' dtype is required")
+        if n is not None and t.numel() != n:
+            raise DsortError(f"{what}: {t.numel()} elements, expected {n}")
+        return t
+
+    def sort_dev(self, t, out=None, descending=False, key_type=None):
+        """Sort a CUDA tensor in place, or into `out` (dsort_sort_dev[_copy]_i32 / _i64; float and
+        unsigned dtypes, a `key_type` override such as "u32" on an int32 tensor, or descending=True:
+        dsort_sort_dev[_copy]_keys).  Floats sort in IEEE totalOrder (dsort.h)."""
+        name, typed = self._tkey(t, key_type, descending)
+        if typed:
+            kt, fl = KEY_TYPES[name], ORDER_DESCENDING if descending else 0
+            if out is None:
+                self.check(self.lib.dsort_sort_dev_keys(self.h, t.data_ptr(), t.numel(), kt, fl, self._stream()))
+                return t
+            assert out.numel() == t.numel() and out.dtype == t.dtype
+            self.check(self.lib.dsort_sort_dev_copy_keys(self.h, t.data_ptr(), out.data_ptr(), t.numel(), kt, fl,
+                                                         self._stream()))
+            return out
+        sfx = name
         if out is None:
             self.check(getattr(self.lib, f"dsort_sort_dev_{sfx}")(self.h, t.data_ptr(), t.numel(),
                                                                    self._stream()))
@@ -539,12 +642,26 @@ class Context:
             raise DsortError(f"{what}: {t.numel()} elements, expected {n}")
         return t
 
-    def argsort_dev(self, keys, idx_out=None, keys_out=None):
+    def argsort_dev(self, keys, idx_out=None, keys_out=None, descending=False, key_type=None):
         """Stable argsort of an int32 or int64 CUDA tensor (dsort_argsort_dev_i32 / _i64): returns
         (keys_out, idx).  idx[j] is the position in `keys` of the j-th smallest key, equal keys
         in input order.  idx is an int32 tensor holding the uint32 bit pattern (torch has no
         uint32 arithmetic): non-negative, and usable as an index, for n < 2^31.  keys_out=None:
-        the sorted keys are not produced (None is returned for them); keys_out may be `keys`."""
+        the sorted keys are not produced (None is returned for them); keys_out may be `keys`.
+        Float and unsigned keys, a `key_type` override or descending=True go to
+        dsort_argsort_dev_keys: the order of dsort.h's "Key types and order", equal keys in ascending
+        input position in either direction."""
+        name, typed = self._tkey(keys, key_type, descending)
+        if typed:
+            n = self._keys1d(keys, "keys").numel()
+            if idx_out is None:
+                idx_out = torch.empty(n, dtype=torch.int32, device=keys.device)
+            self._i32(idx_out, "idx_out", n)
+            ko = None if keys_out is None else self._keys1d(keys_out, "keys_out", n, keys).data_ptr()
+            self.check(self.lib.dsort_argsort_dev_keys(self.h, keys.data_ptr(), ko, idx_out.data_ptr(), n,
+                                                       KEY_TYPES[name], ORDER_DESCENDING if descending else 0,
+                                                       self._stream()))
+            return keys_out, idx_out
         kt = torch.int64 if keys.dtype == torch.int64 else torch.int32
         n = self._i32(keys, "keys", dtype=kt).numel()
         if idx_out is None:
@@ -555,12 +672,16 @@ class Context:
         self.check(f(self.h, keys.data_ptr(), ko, idx_out.data_ptr(), n, self._stream()))
         return keys_out, idx_out
 
-    def sort_records_dev(self, keys, records, keys_out=None, out=None):
+    def sort_records_dev(self, keys, records, keys_out=None, out=None, descending=False, key_type=None):
         """Stable sort of records by an int64 key (dsort_sort_records_dev_i64): records[i] belongs
         to keys[i]; a record is one row of `records`, of 4, 8 or 16 bytes as for gather_dev; rows of
         equal keys keep their input order.  keys_out (None: not wanted; may be `keys`) gets the
-        sorted keys.  Returns (keys_out, out), out holding the rows in key order."""
-        n = self._i32(keys, "keys", dtype=torch.int64).numel()
+        sorted keys.  Returns (keys_out, out), out holding the rows in key order.  Float and unsigned
+        keys, a `key_type` override (key_type="i32": the record sort of int32 keys) or
+        descending=True: dsort_sort_records_dev_keys."""
+        name, typed = self._tkey(keys, key_type, descending)
+        typed = typed or key_type is not None
+        n = self._keys1d(keys, "keys").numel() if typed else self._i32(keys, "keys", dtype=torch.int64).numel()
         if not records.is_contiguous() or records.dim() < 1 or int(records.shape[0]) != n:
             raise DsortError("sort_records_dev: one contiguous record per key is required")
         rec = records.element_size()
@@ -572,15 +693,32 @@ class Context:
             out = torch.empty_like(records)
         if out.dtype != records.dtype or out.shape != records.shape or not out.is_contiguous():
             raise DsortError("sort_records_dev: out must match the records' type and shape")
+        if typed:
+            ko = None if keys_out is None else self._keys1d(keys_out, "keys_out", n, keys).data_ptr()
+            self.check(self.lib.dsort_sort_records_dev_keys(self.h, keys.data_ptr(), ko, records.data_ptr(),
+                                                            out.data_ptr(), n, rec, KEY_TYPES[name],
+                                                            ORDER_DESCENDING if descending else 0, self._stream()))
+            return keys_out, out
         ko = None if keys_out is None else self._i32(keys_out, "keys_out", n, torch.int64).data_ptr()
         self.check(self.lib.dsort_sort_records_dev_i64(self.h, keys.data_ptr(), ko, records.data_ptr(),
                                                        out.data_ptr(), n, rec, self._stream()))
         return keys_out, out
 
-    def sort_pairs_dev(self, keys, vals, keys_out=None, vals_out=None):
+    def sort_pairs_dev(self, keys, vals, keys_out=None, vals_out=None, descending=False, key_type=None):
         """Key-value sort of int32 CUDA tensors (dsort_sort_pairs_dev_i32): ascending by key, equal
         keys by value as UNSIGNED 32-bit.  In place when the outputs are None.  Returns
-        (keys_out, vals_out)."""
+        (keys_out, vals_out).  float32 / uint32 keys, a `key_type` override or descending=True:
+        dsort_sort_pairs_dev_keys (4-byte key types only; equal keys still by value ascending)."""
+        name, typed = self._tkey(keys, key_type, descending)
+        if typed:
+            n = self._keys1d(keys, "keys").numel()
+            self._i32(vals, "vals", n)
+            keys_out = keys if keys_out is None else self._keys1d(keys_out, "keys_out", n, keys)
+            vals_out = vals if vals_out is None else self._i32(vals_out, "vals_out", n)
+            self.check(self.lib.dsort_sort_pairs_dev_keys(self.h, keys.data_ptr(), vals.data_ptr(), keys_out.data_ptr(),
+                                                          vals_out.data_ptr(), n, KEY_TYPES[name],
+                                                          ORDER_DESCENDING if descending else 0, self._stream()))
+            return keys_out, vals_out
         n = self._i32(keys, "keys").numel()
         self._i32(vals, "vals", n)
         keys_out = keys if keys_out is None else self._i32(keys_out, "keys_out", n)
@@ -607,9 +745,21 @@ class Context:
                                              self._stream()))
         return out
 
-    def argsort(self, keys):
+    def argsort(self, keys, descending=False, key_type=None):
         """Host form (dsort_argsort_i32 / _i64): stable argsort of a numpy array -- int64 as it is,
-        anything else as int32; returns (sorted_keys, idx) as new arrays, idx of dtype uint32."""
+        anything else as int32; returns (sorted_keys, idx) as new arrays, idx of dtype uint32.
+        float32 / float64 / uint32 / uint64 arrays, a `key_type` override or descending=True:
+        dsort_argsort_keys on the array as it is."""
+        typed = descending or key_type is not None or (
+            isinstance(keys, np.ndarray) and _KEY_OF_NP.get(keys.dtype) in ("u32", "f32", "u64", "f64"))
+        if typed:
+            keys = np.ascontiguousarray(keys)
+            name = _np_key(keys, key_type)
+            out = np.empty_like(keys)
+            idx = np.empty(keys.size, np.uint32)
+            self.check(self.lib.dsort_argsort_keys(self.h, _ptr(keys), _ptr(out), _ptr(idx), keys.size,
+                                                   KEY_TYPES[name], ORDER_DESCENDING if descending else 0))
+            return out, idx
         wide = isinstance(keys, np.ndarray) and keys.dtype == np.int64
         keys = np.ascontiguousarray(keys, np.int64 if wide else np.int32)
         out = np.empty_like(keys)
@@ -719,10 +869,18 @@ class Context:
     def comm_abort(self):
         self.check(self.lib.dsort_comm_abort(self.h))
 
-    def sample_sort_dev(self, t):
-        """Returns (device pointer int, n_out) of this rank's slice (context-owned)."""
-        sfx = self._tsfx(t)
+    def sample_sort_dev(self, t, descending=False, key_type=None):
+        """Returns (device pointer int, n_out) of this rank's slice (context-owned).  Float and
+        unsigned keys, a `key_type` override or descending=True: dsort_sample_sort_dev_keys, the
+        slice holding keys of the input's type."""
+        name, typed = self._tkey(t, key_type, descending)
         outp, nout = P(), SZ()
+        if typed:
+            self.check(self.lib.dsort_sample_sort_dev_keys(self.h, t.data_ptr() if t.numel() else None, t.numel(),
+                                                           KEY_TYPES[name], ORDER_DESCENDING if descending else 0,
+                                                           ctypes.byref(outp), ctypes.byref(nout), self._stream()))
+            return outp.value or 0, nout.value
+        sfx = name
         self.check(getattr(self.lib, f"dsort_sample_sort_dev_{sfx}")(self.h, t.data_ptr(), t.numel(),
                                                                       ctypes.byref(outp), ctypes.byref(nout),
                                                                       self._stream()))
@@ -752,23 +910,33 @@ class Context:
             outs.append(t)
         return outs
 
-    def sample_argsort_dev(self, keys, first):
+    def sample_argsort_dev(self, keys, first, descending=False, key_type=None):
         """Global stable argsort over the communicator (dsort_sample_argsort_dev_i32 / _i64): `keys`
         is this rank's chunk, int32 or int64, holding the global positions first .. first +
         len(keys) - 1.  Returns (sorted_keys, idx), this rank's slice of the global order as fresh
         CUDA tensors: the keys of the input's type, idx int32 holding global positions as uint32 bit
         patterns, as argsort_dev documents.  DSORT_ESTAGE of the int64 call leaves valid outputs: the
-        DsortError then carries them as `.slices`."""
-        kt = torch.int64 if keys.dtype == torch.int64 else torch.int32
-        n = self._i32(keys, "keys", dtype=kt).numel()
+        DsortError then carries them as `.slices`.  Float and unsigned keys, a `key_type` override or
+        descending=True: dsort_sample_argsort_dev_keys, equal keys in ascending global position."""
+        name, typed = self._tkey(keys, key_type, descending)
         kp, ip, nout = P(), P(), SZ()
-        f = self.lib.dsort_sample_argsort_dev_i64 if kt == torch.int64 else self.lib.dsort_sample_argsort_dev_i32
-        rc = f(self.h, keys.data_ptr() if n else None, n, int(first), ctypes.byref(kp), ctypes.byref(ip),
-               ctypes.byref(nout), self._stream())
+        if typed:
+            kt = keys.dtype
+            n = self._keys1d(keys, "keys").numel()
+            rc = self.lib.dsort_sample_argsort_dev_keys(self.h, keys.data_ptr() if n else None, n, int(first),
+                                                        KEY_TYPES[name], ORDER_DESCENDING if descending else 0,
+                                                        ctypes.byref(kp), ctypes.byref(ip), ctypes.byref(nout),
+                                                        self._stream())
+        else:
+            kt = torch.int64 if keys.dtype == torch.int64 else torch.int32
+            n = self._i32(keys, "keys", dtype=kt).numel()
+            f = self.lib.dsort_sample_argsort_dev_i64 if kt == torch.int64 else self.lib.dsort_sample_argsort_dev_i32
+            rc = f(self.h, keys.data_ptr() if n else None, n, int(first), ctypes.byref(kp), ctypes.byref(ip),
+                   ctypes.byref(nout), self._stream())
         try:
             self.check(rc)
         except DsortError as e:
-            if e.rc == -7 and kt == torch.int64:  # DSORT_ESTAGE: every leg has run
+            if e.rc == -7 and keys.element_size() == 8:  # DSORT_ESTAGE: every leg has run
                 e.slices = tuple(self._slices((kp, ip), nout.value, keys.device, (kt, torch.int32)))
             raise
         k, i = self._slices((kp, ip), nout.value, keys.device, (kt, torch.int32))

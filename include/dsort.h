@@ -20,8 +20,10 @@
  *   - all sizes are size_t (the reference uses int, client.c:166, server.c:481);
  *   - every call returns 0 on success or a negative DSORT_E* code; dsort_last_error(ctx)
  *     gives the message.  Nothing inside the library calls exit() (server.c:485-498 does);
- *   - keys are signed, compared as signed integers, sorted ascending; the full range is valid
- *     (the reference cannot take -1 or INT_MAX);
+ *   - the *_i32 / *_i64 entry points take signed keys, compared as signed integers, sorted
+ *     ascending; the full range is valid (the reference cannot take -1 or INT_MAX).
+ *     The *_keys entry points ("Key types and order" below) take float, unsigned and signed keys of
+ *     4 and 8 bytes, ascending or descending;
  *   - one context per thread; one context drives one GPU.
  */
 #ifndef DSORT_H
@@ -493,6 +495,107 @@ int dsort_sample_argsort_dev_i64(dsort_ctx *ctx, const int64_t *d_keys, size_t n
 int dsort_plan_sample_argsort_i64(int nranks, const uint64_t first[], const uint64_t count[],
                                   const int64_t key_min[], const int64_t key_max[], int *idx_bits,
                                   int *passes);
+
+/* ---------------------------------------------------------------- key types and order --
+ * An ABI 10 addition (new symbols only; no struct, option or existing call changes): every sort
+ * entry for typed keys -- float32, float64, uint32, uint64, int32, int64 -- ascending or descending.
+ *
+ * The codec.  A key's bits b, as an integer of the key's width W, map to a word w whose SIGNED order
+ * is the order of the keys, and back (csrc/dsort_keycodec.h, one rule for host and device):
+ *
+ *     DSORT_KEY_I32, _I64    w = b
+ *     DSORT_KEY_U32, _U64    w = b ^ sign_bit
+ *     DSORT_KEY_F32, _F64    w = b ^ ((b >> (W-1)) & ~sign_bit), the shift arithmetic: a negative
+ *                            float flips every bit but the sign
+ *     DSORT_ORDER_DESCENDING ~w of the ascending word
+ *
+ * Every step is an involution, so decoding applies the same steps in reverse order and the round
+ * trip is bit-exact: NaN payloads and the sign of zero survive a sort.
+ *
+ * The order.  Integers: numeric.  Floats: IEEE 754 totalOrder -- negative NaNs (larger payload
+ * first), -inf, ..., -0.0, +0.0, ..., +inf, positive NaNs (larger payload last).  Descending is the
+ * exact reverse.  This differs from numpy and torch, which treat -0.0 == +0.0 and put every NaN last:
+ *   - -0.0 sorts before +0.0 (descending: after), so an argsort is not stable ACROSS the two zeros;
+ *   - NaNs with the sign bit set come first (descending: last), not last.
+ * Inputs without NaN and without -0.0 give results bit-identical to np.sort,
+ * np.argsort(kind="stable") and torch.sort(stable=True, descending=...).  Stability: keys of equal
+ * BITS keep ascending input position in either order (ties stay ties under ~w), so a stable
+ * descending argsort lists equal keys by ascending position, as torch does.
+ *
+ * The calls.  Each keeps the contract of the integer call of the same width -- dsort_sort_dev_*,
+ * dsort_sort_dev_copy_*, dsort_sort_*, dsort_argsort_dev_*, dsort_argsort_*, dsort_sort_pairs_dev_i32,
+ * dsort_sort_records_dev_i64, dsort_sample_sort_dev_*, dsort_sample_argsort_dev_* -- with "key" now
+ * meaning the typed key and its order the one above: aliasing rules, NULL for d_keys_out, alignment
+ * (elements only), n <= 2^32 for positions, n == 0 touching nothing, the arenas, the stream rules,
+ * DSORT_OPT_KILL_AFTER_STAGE / DSORT_ESTAGE, the statistics (argsort_passes included) and, across
+ * ranks, the collectives with their gates.  Key pointers are void *: n elements of the type's width.
+ * With DSORT_KEY_I32 / _I64 and flags 0 a call IS the integer call.  In addition:
+ *   - an unknown key_type, a flag bit other than DSORT_ORDER_DESCENDING, or an 8-byte type given to
+ *     dsort_sort_pairs_dev_keys is DSORT_EINVAL before any memory or collective is touched; a NULL
+ *     context is a plain DSORT_EINVAL;
+ *   - dsort_sort_pairs_dev_keys: equal keys stay ordered by value as unsigned 32-bit ASCENDING, in
+ *     either key order;
+ *   - dsort_sort_records_dev_keys with a 4-byte type is the argsort into a context arena (4 n bytes)
+ *     and the kernel of dsort_gather_dev -- which also gives int32 keys a record sort; with an
+ *     8-byte type it is dsort_sort_records_dev_i64's path;
+ *   - 8-byte types: the choice between one and two passes is dsort_plan_argsort_i64 applied to the
+ *     min and max of the ENCODED words.  uint64 ids around 2^63 are narrow (the encoding removes the
+ *     sign-bit straddle); float64 values of one binade are narrow, but float64 data that spans many
+ *     binades has a wide encoded range and takes the two-pass path.
+ *
+ * Where the codec runs.  Argsort, pair sort and record sort: inside the pack and unpack kernels
+ * those paths already stream every key through -- no extra pass over memory.  The keys-only sorts
+ * (dsort_sort_dev_keys, _copy_keys, dsort_sort_keys): an encode kernel, the integer sort, a decode
+ * kernel, i.e. two extra streaming passes over the keys (the out-of-place form encodes d_in into
+ * d_out and sorts and decodes d_out in place: no arena, d_in unmodified); signed keys ascending
+ * call the integer sort directly.  Across ranks: this rank's chunk is encoded into a grow-only
+ * context arena of its own (n_local elements), the integer sample sort / sample argsort runs on it,
+ * and the returned key slice is decoded in place on `stream` -- context-owned and ready after the
+ * stream, as it is for the integer call.  A rank with n_local == 0 still joins every collective.
+ * Ranks that disagree on key_type or flags are the caller's error and are NOT checked: the result
+ * is then not an order of anything.
+ *
+ * Not offered: the codec fused into the keys-only sort's own kernels; typed keys in the C master and
+ * workers and in the text codec. */
+#define DSORT_KEY_I32 0
+#define DSORT_KEY_U32 1
+#define DSORT_KEY_F32 2
+#define DSORT_KEY_I64 3
+#define DSORT_KEY_U64 4
+#define DSORT_KEY_F64 5
+#define DSORT_ORDER_DESCENDING 1   /* flags bit 0; every other bit must be 0 */
+
+/* The host rule, exported so that the CPU tests run the code the GPU runs: words[i] = the codec's
+ * word of keys[i] (a signed integer of the key's width) and back; words may alias keys.  No
+ * context.  DSORT_EINVAL, nothing written: an unknown key_type or flag bit, a NULL array with
+ * n > 0. */
+int dsort_key_encode(int key_type, int flags, const void *keys, void *words, size_t n);
+int dsort_key_decode(int key_type, int flags, const void *words, void *keys, size_t n);
+
+/* keys only: in place, out of place (d_in may equal d_out), and from a host buffer (staged) */
+int dsort_sort_dev_keys(dsort_ctx *ctx, void *d_keys, size_t n, int key_type, int flags, void *stream);
+int dsort_sort_dev_copy_keys(dsort_ctx *ctx, const void *d_in, void *d_out, size_t n, int key_type,
+                             int flags, void *stream);
+int dsort_sort_keys(dsort_ctx *ctx, void *host_keys, size_t n, int key_type, int flags);
+/* stable argsort, device and host form */
+int dsort_argsort_dev_keys(dsort_ctx *ctx, const void *d_keys, void *d_keys_out, uint32_t *d_idx_out,
+                           size_t n, int key_type, int flags, void *stream);
+int dsort_argsort_keys(dsort_ctx *ctx, const void *keys, void *keys_out, uint32_t *idx, size_t n,
+                       int key_type, int flags);
+/* key-value sort: 4-byte key types only */
+int dsort_sort_pairs_dev_keys(dsort_ctx *ctx, const void *d_keys_in, const uint32_t *d_vals_in,
+                              void *d_keys_out, uint32_t *d_vals_out, size_t n, int key_type, int flags,
+                              void *stream);
+/* stable record sort, records of 4, 8 or 16 bytes */
+int dsort_sort_records_dev_keys(dsort_ctx *ctx, const void *d_keys, void *d_keys_out, const void *d_src,
+                                void *d_dst, size_t n, int elem_bytes, int key_type, int flags,
+                                void *stream);
+/* across ranks */
+int dsort_sample_sort_dev_keys(dsort_ctx *ctx, const void *d_keys, size_t n_local, int key_type,
+                               int flags, void **d_out, size_t *n_out, void *stream);
+int dsort_sample_argsort_dev_keys(dsort_ctx *ctx, const void *d_keys, size_t n_local, uint64_t first,
+                                  int key_type, int flags, void **d_keys_out, uint32_t **d_idx_out,
+                                  size_t *n_out, void *stream);
 
 /* ABI 9: the distributed record gather -- payloads follow their keys across ranks.
  *   d_dst[j] = the record at GLOBAL position d_idx[j], j < n_idx, wherever it lives.

@@ -50,6 +50,18 @@ process, results compared bit for bit: ms per call, the legs of both from the li
 unpack, the two splits, regroup, final -- as fractions of a device-to-device copy of the same byte
 total in the same run (bench_sample_i64).
 
+    python scripts/bench_pairs.py --typed [--log2 28] [--steps 10] [--out profiles/pairs_typed_bench.json]
+
+--typed measures typed keys and descending order (dsort.h, "Key types and order"; bench_typed).  Fused
+paths, at every --log2 size (default 2^28): argsort_dev of float32 keys -- the uniform int32 keys of
+the default mode, the same bits -- ascending and descending beside the int32 argsort_dev of those bits
+in the same process; the same for float64 on the bits of --i64's wide keys and on narrow keys of one
+binade (1.0 + j 2^-52, j < 2^34) beside int64 keys of the same range; every result checked against
+the integer argsort of the encoded words.  Keys-only path, at 2^28 and 2^30: the encode and the
+decode kernel alone for 4- and 8-byte keys (float, descending), each as a ratio to a device-to-device
+copy of the same bytes in the same run, and sort_dev of 2^30 float32 keys beside the int32 sort_dev
+of the same bits and torch.sort of the same tensor.
+
 Writes the JSON file and prints one summary line.  No GPU: fails (there is nothing to measure).
 """
 import argparse
@@ -461,6 +473,119 @@ def bench_sample_i64(torch, dsort, ctx, n, steps, warmup):
     return {"n": n, "leg_bytes_per_element": S64_LEG_BYTES, "inputs": inputs}
 
 
+def bench_typed(torch, dsort, ctx, n, steps, warmup):
+    """--typed, the fused paths at n keys: the typed argsort beside the integer argsort of the same
+    bits (float32, float64 wide) or of the same range (float64 narrow) in one process."""
+    r4 = lambda x: round(x, 4)  # noqa: E731
+    res = {"n": n}
+
+    def run(keys, **kw):
+        out = torch.empty_like(keys)
+        idx = torch.empty(n, dtype=torch.int32, device="cuda")
+        ms = timed(torch, lambda: ctx.argsort_dev(keys, idx_out=idx, keys_out=out, **kw), steps, warmup)
+        return ms, out, idx, ctx.stats()["argsort_passes"]
+
+    def check(keys, out, idx, name, desc):
+        """The typed result against the integer argsort of the encoded words, computed on the device."""
+        W = keys.element_size() * 8
+        it = torch.int32 if W == 32 else torch.int64
+        b = keys.view(it)
+        w = b ^ ((b >> (W - 1)) & ((1 << (W - 1)) - 1)) if name[0] == "f" else b
+        w = ~w if desc else w
+        _, ridx = ctx.argsort_dev(w.contiguous(), keys_out=None)
+        ok = bool(torch.equal(idx, ridx))
+        ok = ok and bool(torch.equal(out.view(it), b[ridx.to(torch.int64)]))
+        del w, ridx
+        torch.cuda.empty_cache()
+        return ok
+
+    def family(label, ikeys, fkeys, name):
+        fam = {}
+        ms, out, idx, passes = run(ikeys)
+        fam["int_asc"] = {"argsort_ms": r4(ms), "argsort_passes": passes}
+        del out, idx
+        for desc in (False, True):
+            ms, out, idx, passes = run(fkeys, descending=desc)
+            fam[name + ("_desc" if desc else "_asc")] = {
+                "argsort_ms": r4(ms), "argsort_passes": passes, "over_int_asc": r4(ms / fam["int_asc"]["argsort_ms"]),
+                "exact_vs_int_argsort_of_encoded_words": check(fkeys, out, idx, name, desc)}
+            del out, idx
+            torch.cuda.empty_cache()
+        ms2, out, idx, _ = run(ikeys)  # the integer call again, after the typed ones
+        fam["int_asc_again"] = {"argsort_ms": r4(ms2)}
+        del out, idx
+        torch.cuda.empty_cache()
+        res[label] = fam
+
+    k32 = torch.empty(n, dtype=torch.int32, device="cuda")
+    ctx.gen_uniform(k32, 0x5EED2026, 0)
+    family("f32_uniform_bits", k32, k32.view(torch.float32), "f32")
+    del k32
+    torch.cuda.empty_cache()
+    k64 = torch.empty(n, dtype=torch.int64, device="cuda")
+    ctx.gen_uniform(k64, 0x5EED2026, 0)
+    family("f64_wide_uniform_bits", k64, k64.view(torch.float64), "f64")
+    k64 >>= 30  # --i64's narrow keys, uniform in [-2^33, 2^33)
+    one = torch.tensor([1.0], dtype=torch.float64).view(torch.int64).item()
+    f64 = (k64 + ((1 << 33) + one)).view(torch.float64)  # 1.0 + j 2^-52, j < 2^34: one binade
+    family("f64_narrow_one_binade", k64, f64, "f64")
+    return res
+
+
+def bench_keys_only(torch, dsort, ctx, lg, steps, warmup):
+    """--typed, the keys-only path at 2^lg keys: the encode and decode kernels alone against a
+    device-to-device copy of the same bytes; at 2^30 also the whole float32 sort_dev."""
+    n = 1 << lg
+    r4 = lambda x: round(x, 4)  # noqa: E731
+    hook = ctx.lib.dsort_keys_code_dev  # not in dsort.h: the bench's view of the two kernels
+    hook.restype = ctypes.c_int
+    hook.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+                     ctypes.c_int, ctypes.c_void_p]
+    res = {"n": n}
+    for W, kt in ((4, dsort.KEY_TYPES["f32"]), (8, dsort.KEY_TYPES["f64"])):
+        src = torch.empty(n * W, dtype=torch.uint8, device="cuda")
+        dst = torch.empty_like(src)
+        src.zero_()
+        copy_ms = timed(torch, lambda: dst.copy_(src), steps, warmup)
+        entry = {"bytes_read_plus_written": 2 * W * n, "memcpy_ms": r4(copy_ms),
+                 "memcpy_gb_per_s": r4(2 * W * n / (copy_ms * 1e-3) / 1e9)}
+        for what, dec in (("encode", 0), ("decode", 1)):
+            oop = timed(torch, lambda: ctx.check(hook(ctx.h, src.data_ptr(), dst.data_ptr(), n, kt, 1, dec,
+                                                       ctx._stream())), steps, warmup)
+            inp = timed(torch, lambda: ctx.check(hook(ctx.h, dst.data_ptr(), dst.data_ptr(), n, kt, 1, dec,
+                                                       ctx._stream())), steps, warmup)
+            entry[what] = {"out_of_place_ms": r4(oop), "in_place_ms": r4(inp),
+                           "out_of_place_over_memcpy": r4(oop / copy_ms), "in_place_over_memcpy": r4(inp / copy_ms)}
+        res[f"{W}_byte_keys"] = entry
+        del src, dst
+        torch.cuda.empty_cache()
+    if lg == 30:
+        bits = torch.empty(n, dtype=torch.int32, device="cuda")
+        ctx.gen_uniform(bits, 0x5EED2026, 0)
+        work = torch.empty_like(bits)
+        whole = {}
+        whole["int32_sort_dev_ms"] = r4(timed(torch, lambda: ctx.sort_dev(bits, out=work), steps, warmup))
+        fk, fw = bits.view(torch.float32), work.view(torch.float32)
+        for desc in (False, True):
+            ms = timed(torch, lambda: ctx.sort_dev(fk, out=fw, descending=desc), steps, warmup)
+            whole["float32_sort_dev_desc_ms" if desc else "float32_sort_dev_asc_ms"] = r4(ms)
+        # the check: the words of the sorted floats ascend (descending: descend) and are a permutation
+        ctx.sort_dev(fk, out=fw, descending=False)
+        w = work ^ ((work >> 31) & 0x7FFFFFFF)
+        whole["sorted_in_total_order"] = bool((w[1:] >= w[:-1]).all()) and ctx.fingerprint(work) == ctx.fingerprint(bits)
+        del w, work, fw
+        torch.cuda.empty_cache()
+        # torch.sort of the same tensor; the NaNs among uniform bits go last there, so NaN-free keys too
+        whole["torch_sort_same_bits_ms"] = r4(timed(torch, lambda: torch.sort(fk), max(3, steps // 2), 1))
+        torch.cuda.empty_cache()
+        whole["float32_over_int32"] = r4(whole["float32_sort_dev_asc_ms"] / whole["int32_sort_dev_ms"])
+        whole["torch_over_float32_sort_dev"] = r4(whole["torch_sort_same_bits_ms"] / whole["float32_sort_dev_asc_ms"])
+        res["sort_dev_float32"] = whole
+        del bits, fk
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2", type=int, nargs="+", default=None)
@@ -478,12 +603,17 @@ def main():
     ap.add_argument("--sample-i64", action="store_true",
                     help="time dsort_sample_argsort_dev_i64 on one RCCL rank, narrow and wide keys, against "
                          "dsort_argsort_dev_i64 (default 2^28 keys, profiles/pairs_sample_i64_bench.json)")
+    ap.add_argument("--typed", action="store_true",
+                    help="time typed keys: argsort_dev of float32 / float64 keys, ascending and descending, beside the "
+                         "integer argsort of the same bits (default 2^28 keys), and the keys-only path's encode and "
+                         "decode kernels and float32 sort_dev at 2^28 and 2^30 (profiles/pairs_typed_bench.json)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.log2 = args.log2 or ([28] if args.sample or args.gather or args.sample_i64 else [28, 30])
+    args.log2 = args.log2 or ([28] if args.sample or args.gather or args.sample_i64 or args.typed else [28, 30])
     name = "pairs_gather_bench.json" if args.gather else "pairs_sample_bench.json" if args.sample else "pairs_bench.json"
     name = "pairs_i64_bench.json" if args.i64 else name
     name = "pairs_sample_i64_bench.json" if args.sample_i64 else name
+    name = "pairs_typed_bench.json" if args.typed else name
     args.out = args.out or os.path.join(REPO, "profiles", name)
 
     import torch
@@ -493,6 +623,31 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_pairs: no GPU visible (nothing is measured without one)")
     ctx = dsort.Context(0)
+    if args.typed:
+        res = {"what": "typed keys (dsort.h, Key types and order), resident in HBM.  fused: argsort_dev (sorted keys and "
+                       "indices) of float keys, ascending and descending, beside the integer argsort_dev of the same "
+                       "bits (f64 narrow: of the same range) in the same process, ms per call of --steps back-to-back "
+                       "calls.  keys_only: the encode / decode kernel alone against a device-to-device copy of the "
+                       "same bytes, and sort_dev of 2^30 float32 keys beside the int32 sort_dev of the same bits and "
+                       "torch.sort of the same tensor",
+               "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup,
+               "fused": [bench_typed(torch, dsort, ctx, 1 << lg, args.steps, args.warmup) for lg in args.log2],
+               "keys_only": [bench_keys_only(torch, dsort, ctx, lg, args.steps, args.warmup) for lg in (28, 30)]}
+        ctx.close()
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"pairs_typed_bench": {
+            "fused": [{"n": s["n"], **{fam: {k: v["argsort_ms"] for k, v in s[fam].items()} for fam in s if fam != "n"},
+                       "exact": all(v.get("exact_vs_int_argsort_of_encoded_words", True)
+                                    for fam in s if fam != "n" for v in s[fam].values())} for s in res["fused"]],
+            "keys_only": [{"n": s["n"],
+                           **{k: {w: s[k][w]["out_of_place_over_memcpy"] for w in ("encode", "decode")}
+                              for k in ("4_byte_keys", "8_byte_keys")},
+                           **({"sort_dev_float32": s["sort_dev_float32"]} if "sort_dev_float32" in s else {})}
+                          for s in res["keys_only"]]}}), flush=True)
+        return
     if args.sample_i64:
         res = {"what": "global stable argsort of int64 keys on one RCCL rank (dsort_sample_argsort_dev_i64): narrow = "
                        "uniform in [-2^33, 2^33), one pass; wide = uniform over 64 bits, two passes with two distributed "
