@@ -321,6 +321,83 @@ def test_gather_vs_numpy(gpu_ctx, n, rec):
     assert np.array_equal(_host(out), src[perm])
 
 
+def _gather_src(rng, m, rec):
+    if rec == 4:
+        return rng.integers(I32.min, I32.max, m, dtype=np.int32)
+    if rec == 8:
+        return rng.integers(np.iinfo(np.int64).min, np.iinfo(np.int64).max, m, dtype=np.int64)
+    return rng.integers(I32.min, I32.max, (m, 4), dtype=np.int32)
+
+
+def _gather_check(gpu_ctx, src, idx, view=0):
+    """gather_dev against src[idx].  src, idx and out start at element `view` of their allocations;
+    zero guard words of one record around out must stay zero, src and idx unchanged."""
+    import torch
+    n, row = idx.size, src.shape[1:]
+    D = int(np.prod(row, dtype=np.int64))  # elements of one record
+
+    def at(a):  # a device copy that starts at element `view` of its allocation
+        flat = np.ascontiguousarray(a).reshape(-1)
+        t = torch.zeros(view + max(flat.size, 1), dtype=torch.from_numpy(flat[:0]).dtype, device="cuda")
+        t = t[view:view + flat.size]
+        if flat.size:
+            t.copy_(torch.from_numpy(flat))
+        return t
+
+    dsrc, didx = at(src).view(src.shape), at(idx)
+    full = torch.zeros(view + (n + 2) * D, dtype=dsrc.dtype, device="cuda")
+    out = full[view + D:view + D + n * D].view((n,) + row)
+    assert gpu_ctx.gather_dev(dsrc, didx, out) is out
+    torch.cuda.synchronize()
+    assert np.array_equal(_host(out), src[idx.view(np.uint32).astype(np.int64)])
+    full_h = _host(full)
+    assert not full_h[:view + D].any() and not full_h[view + D + n * D:].any()
+    assert np.array_equal(_host(dsrc), src) and np.array_equal(_host(didx), idx)
+
+
+GATHER_TRIP = 2048 * 256  # lanes of one trip of gather_kernel's grid: a lane moves 16 / W records
+
+
+@pytest.mark.parametrize("rec,sizes", [(4, [0, 2, 4, 6, 256, 258]), (8, [0, 2, 256]), (16, [0, 1, 256])])
+def test_gather_tails_and_repeated_indices(gpu_ctx, rec, sizes):
+    """n without a tail, with a tail of 2 records at W = 4, nothing at all; a permutation that names
+    the source's last record, one index n times, indices drawn from 3 positions."""
+    rng = np.random.default_rng(rec)
+    for n in sizes:
+        m = n + 5
+        src = _gather_src(rng, m, rec)
+        perm = rng.permutation(m)[:n]
+        if n:
+            perm[rng.integers(0, n)] = m - 1
+        for idx in (perm, np.full(n, m - 1), np.full(n, 2), rng.choice(np.array([0, m // 2, m - 1]), n)):
+            _gather_check(gpu_ctx, src, idx.astype(np.int32))
+
+
+@pytest.mark.parametrize("rec", [4, 8, 16])
+def test_gather_past_one_trip_of_the_grid(gpu_ctx, rec):
+    """257 records more than 2048 workgroups of 256 lanes move in one trip: the grid-stride loop wraps,
+    and a tail remains (one record at W = 4 and 8).  Indices with repeats, the last record among them."""
+    n = GATHER_TRIP * (16 // rec) + 257
+    rng = np.random.default_rng(40 + rec)
+    m = 100_003
+    src = _gather_src(rng, m, rec)
+    idx = rng.integers(0, m, n)
+    idx[[0, n // 2, n - 1]] = m - 1
+    _gather_check(gpu_ctx, src, idx.astype(np.int32))
+
+
+@pytest.mark.parametrize("rec", [4, 16])
+def test_gather_views_at_element_offsets(gpu_ctx, rec):
+    """src, idx and out start 1 and 3 elements into their allocations: dword alignment only."""
+    rng = np.random.default_rng(60 + rec)
+    for view in (1, 3):
+        for n in (6, 258, 1027):
+            src = _gather_src(rng, n + 5, rec)
+            idx = rng.integers(0, n + 5, n)
+            idx[n // 2] = n + 4
+            _gather_check(gpu_ctx, src, idx.astype(np.int32), view)
+
+
 def test_gather_rejects_other_record_sizes(gpu_ctx, dsort_mod):
     import torch
     idx = torch.zeros(4, dtype=torch.int32, device="cuda")
