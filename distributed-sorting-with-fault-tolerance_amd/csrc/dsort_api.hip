@@ -397,7 +397,8 @@ int dsort_finalize(dsort_ctx *ctx) {
                     ctx->bucket, ctx->sub, ctx->sub_alt, ctx->stmp, ctx->bxs, ctx->tfb, ctx->fence, ctx->pairs,
                     ctx->spairs_k, ctx->spairs_v, ctx->gat_req, ctx->gat_rreq, ctx->gat_rep, ctx->gat_back,
                     ctx->gat_small, ctx->a64_b, ctx->a64_idx, ctx->a64_part, ctx->s64_k, ctx->s64_i,
-                    ctx->s64_sa, ctx->s64_pos, ctx->s64_got, ctx->kenc};
+                    ctx->s64_sa, ctx->s64_pos, ctx->s64_got, ctx->kenc, ctx->tk_rows, ctx->tk_small,
+                    ctx->tk_ck, ctx->tk_cp, ctx->tk_rk, ctx->tk_rp, ctx->tk_sk};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->red_host) (void)hipHostFree(ctx->red_host);
@@ -426,6 +427,8 @@ int dsort_finalize(dsort_ctx *ctx) {
     for (auto &e : ctx->a64_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : ctx->s64_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : ctx->tk_ev)
         if (e) (void)hipEventDestroy(e);
     if (ctx->a64_mm_ev) (void)hipEventDestroy(ctx->a64_mm_ev);
     for (auto &e : ctx->ev)
@@ -512,6 +515,10 @@ int dsort_set_option(dsort_ctx *ctx, int option, int64_t v) {
             if (v < -1) return set_err(ctx, DSORT_EINVAL, "DSORT_OPT_TEST_FAIL_LEG: -1 or a leg index");
             o.test_fail_leg = v;
             return DSORT_OK;
+        case DSORT_OPT_TOPK_PATH:
+            if (v < -1 || v > 1) return set_err(ctx, DSORT_EINVAL, "DSORT_OPT_TOPK_PATH: -1, 0 or 1");
+            o.topk_path = v;
+            return DSORT_OK;
         default:
             return set_err(ctx, DSORT_EINVAL, "unknown option " + std::to_string(option));
     }
@@ -538,6 +545,7 @@ int dsort_get_option(const dsort_ctx *ctx, int option, int64_t *v) {
         case DSORT_OPT_SUB_GATHER: *v = o.sub_gather; return DSORT_OK;
         case DSORT_OPT_ARGSORT_WIDE: *v = o.argsort_wide; return DSORT_OK;
         case DSORT_OPT_TEST_FAIL_LEG: *v = o.test_fail_leg; return DSORT_OK;
+        case DSORT_OPT_TOPK_PATH: *v = o.topk_path; return DSORT_OK;
         default: return DSORT_EINVAL;
     }
 }

@@ -70,6 +70,7 @@ struct dsort_opts {
     int64_t sub_gather = 1;         // DSORT_OPT_SUB_GATHER
     int64_t argsort_wide = 0;       // DSORT_OPT_ARGSORT_WIDE
     int64_t test_fail_leg = -1;     // DSORT_OPT_TEST_FAIL_LEG
+    int64_t topk_path = -1;         // DSORT_OPT_TOPK_PATH: -1 dsort_plan_topk's rule, 0 full argsort, 1 select
 };
 
 // The context.  One per host thread, bound to one device.
@@ -141,6 +142,25 @@ struct dsort_ctx {
     // input of the integer call behind them
     void *kenc = nullptr;
     size_t kenc_bytes = 0;
+    // top-k selection (dsort_topk.hip); the 4-byte candidates' packed words go to `pairs`, the order
+    // of the 8-byte candidates to `a64_idx`
+    void *tk_rows = nullptr;      // one pass's histogram rows: 2048 bins per workgroup (4 B each)
+    size_t tk_rows_bytes = 0;
+    void *tk_small = nullptr;     // the state, the partial column sums, less / eq / quota / offsets
+    size_t tk_small_bytes = 0;
+    void *tk_ck = nullptr;        // the candidates: 8-byte keys, or the packed words a rank sends (8 B each);
+    size_t tk_ck_bytes = 0;       // the full path's sorted keys
+    void *tk_cp = nullptr;        // ... and the positions of 8-byte candidates (4 B each)
+    size_t tk_cp_bytes = 0;
+    void *tk_rk = nullptr;        // across ranks, 8-byte keys: every rank's candidates ...
+    size_t tk_rk_bytes = 0;
+    void *tk_rp = nullptr;        // ... their positions ...
+    size_t tk_rp_bytes = 0;
+    void *tk_sk = nullptr;        // ... and the candidates in key order
+    size_t tk_sk_bytes = 0;
+    hipEvent_t tk_ev[14] = {};    // around the select's histogram kernels and compaction (on request)
+    bool tk_timing = false;       // dsort_topk_leg_timing
+    int tk_passes = 0;            // histogram passes the last select timed (0: none)
     // the distributed gather (dsort_gather.hip): arenas of its own, so that a gather leaves the
     // slices of the preceding sample sort / argsort (recv2, spairs_k, spairs_v) alone
     void *gat_req = nullptr;      // this rank's requests, owner-major (4 B per index)
@@ -317,6 +337,10 @@ int sample_sort_packed(dsort_ctx *ctx, const int64_t *d_in, size_t n_local, int6
 namespace pr {
 int pairs_sort(dsort_ctx *ctx, const int32_t *keys_in, const uint32_t *vals_in, int32_t *keys_out,
                uint32_t *vals_out, size_t n, hipStream_t s, int kc = 0);
+// The pair sort's unpack alone, for the top-k select (dsort_topk.hip): keys_out[i] = the decoded high
+// word (NULL: not wanted), vals_out[i] = the low word of packed[i], i < n.
+int unpack_words(dsort_ctx *ctx, const uint64_t *packed, int32_t *keys_out, uint32_t *vals_out, size_t n,
+                 hipStream_t s, int kc);
 }
 namespace p64 {
 int argsort64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uint32_t *idx_out, size_t n, hipStream_t s,

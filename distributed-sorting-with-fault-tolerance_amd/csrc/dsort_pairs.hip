@@ -455,5 +455,17 @@ static void launch_unpack_keys(int kc, unsigned grid, hipStream_t s, const uint6
                                            keys_out, vals_out, n));
 }
 
+int unpack_words(dsort_ctx *ctx, const uint64_t *packed, int32_t *keys_out, uint32_t *vals_out, size_t n,
+                 hipStream_t s, int kc) {
+    if (n == 0) return DSORT_OK;
+    const unsigned grid = grid_for((n + 3) / 4);
+    if (kc)
+        launch_unpack_keys(kc, grid, s, packed, keys_out, vals_out, (uint64_t)n);
+    else
+        hipLaunchKernelGGL(pairs_unpack_kernel, dim3(grid), dim3(NT), 0, s, packed, keys_out, vals_out, (uint64_t)n);
+    DSORT_HIP(ctx, hipGetLastError());
+    return DSORT_OK;
+}
+
 }  // namespace pr
 }  // namespace dsort

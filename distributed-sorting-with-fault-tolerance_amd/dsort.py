@@ -52,6 +52,8 @@ EXPORTS = [
     "dsort_key_encode", "dsort_key_decode", "dsort_sort_dev_keys", "dsort_sort_dev_copy_keys",
     "dsort_sort_keys", "dsort_argsort_dev_keys", "dsort_argsort_keys", "dsort_sort_pairs_dev_keys",
     "dsort_sort_records_dev_keys", "dsort_sample_sort_dev_keys", "dsort_sample_argsort_dev_keys",
+    # top-k selection (an ABI 10 addition)
+    "dsort_plan_topk", "dsort_topk_dev_keys", "dsort_topk_keys", "dsort_sample_topk_dev_keys",
 ]
 
 # DSORT_KEY_* and DSORT_ORDER_DESCENDING (include/dsort.h, "Key types and order")
@@ -68,7 +70,7 @@ OPTIONS = {"buckets": 1, "bucket_keys": 2, "bucket_oversample": 3,
            "comm_timeout_ms": 8,
            "sub_keys": 9, "sub_oversample": 10, "sub_gather": 11, "test_hold_exchange": 12,
            "test_fail_exchange": 13, "stage_timing": 14, "test_tile_cap": 15,
-           "test_wave_fence": 16, "argsort_wide": 17, "test_fail_leg": 18}
+           "test_wave_fence": 16, "argsort_wide": 17, "test_fail_leg": 18, "topk_path": 19}
 
 
 class DsortError(RuntimeError):
@@ -307,6 +309,11 @@ def load():
                                                       ctypes.POINTER(SZ), P]),
         "dsort_sample_argsort_dev_keys": (ctypes.c_int, [P, P, SZ, U64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(P),
                                                          ctypes.POINTER(P), ctypes.POINTER(SZ), P]),
+        "dsort_plan_topk": (ctypes.c_int, [SZ, SZ, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                           ctypes.POINTER(ctypes.c_int)]),
+        "dsort_topk_dev_keys": (ctypes.c_int, [P, P, SZ, SZ, ctypes.c_int, ctypes.c_int, P, P, P]),
+        "dsort_topk_keys": (ctypes.c_int, [P, P, SZ, SZ, ctypes.c_int, ctypes.c_int, P, P]),
+        "dsort_sample_topk_dev_keys": (ctypes.c_int, [P, P, SZ, U64, SZ, ctypes.c_int, ctypes.c_int, P, P, P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)
@@ -458,6 +465,16 @@ def plan_sample_argsort_i64(first, count, key_min, key_max):
     _check(None, load().dsort_plan_sample_argsort_i64(first.size, _ptr(first), _ptr(count), _ptr(key_min),
                                                       _ptr(key_max), ctypes.byref(b), ctypes.byref(p)))
     return b.value, p.value
+
+
+def plan_topk(n, k, key_bytes, path=-1):
+    """The top-k host rule (dsort_plan_topk): (path, digits) for the k first of n keys of key_bytes
+    bytes -- path 0 nothing to do, 1 the select path, 2 the full argsort and its first k; `path`
+    is the value of the "topk_path" option (-1: the rule, 0 / 1: forced); digits = the histogram passes
+    of the select path for the width."""
+    p, d = ctypes.c_int(), ctypes.c_int()
+    _check(None, load().dsort_plan_topk(n, k, key_bytes, path, ctypes.byref(p), ctypes.byref(d)))
+    return p.value, d.value
 
 
 def write_text_i32(path, keys):
@@ -767,6 +784,65 @@ class Context:
         f = self.lib.dsort_argsort_i64 if wide else self.lib.dsort_argsort_i32
         self.check(f(self.h, _ptr(keys), _ptr(out), _ptr(idx), keys.size))
         return out, idx
+
+    # ---------------- top-k selection (dsort.h, "top-k") ------------------------------------
+    def _topk_outs(self, keys, k, keys_out, idx_out):
+        if idx_out is None:
+            idx_out = torch.empty(k, dtype=torch.int32, device=keys.device)
+        self._i32(idx_out, "idx_out", k)
+        if keys_out is None:
+            keys_out = torch.empty(k, dtype=keys.dtype, device=keys.device)
+        elif keys_out is False:  # not wanted: the C call gets NULL
+            keys_out = None
+        else:
+            self._keys1d(keys_out, "keys_out", k, keys)
+        return keys_out, idx_out
+
+    def topk_dev(self, keys, k, descending=False, key_type=None, keys_out=None, idx_out=None):
+        """The first k entries of argsort_dev(keys, descending=..., key_type=...) without the full
+        sort (dsort_topk_dev_keys): returns (keys, idx), both sorted, idx an int32 tensor of uint32
+        bit patterns as argsort_dev documents; descending=True gives the k largest.  Equal keys
+        come in ascending position, and the lowest positions win where the cut falls inside a run
+        of equal keys.  keys_out: a tensor of k elements of the keys' dtype, None (a new one) or
+        False (the keys are not produced and None is returned for them); idx_out: a tensor of k
+        int32, or None for a new one.  The "topk_path" option forces a path."""
+        name, _ = self._tkey(keys, key_type, descending)
+        n = self._keys1d(keys, "keys").numel()
+        if k < 0 or k > n:
+            raise DsortError(f"topk_dev: k = {k} outside 0..{n}")
+        keys_out, idx_out = self._topk_outs(keys, k, keys_out, idx_out)
+        self.check(self.lib.dsort_topk_dev_keys(self.h, keys.data_ptr() if n else None, n, k, KEY_TYPES[name],
+                                                ORDER_DESCENDING if descending else 0,
+                                                keys_out.data_ptr() if keys_out is not None and k else None,
+                                                idx_out.data_ptr() if k else None, self._stream()))
+        return keys_out, idx_out
+
+    def topk(self, host_keys, k, descending=False, key_type=None):
+        """Host form (dsort_topk_keys): the k first of the stable argsort of a numpy array in the
+        typed order; returns (keys, idx) as new arrays, idx of dtype uint32."""
+        keys = np.ascontiguousarray(host_keys)
+        name = _np_key(keys, key_type)
+        if k < 0 or k > keys.size:
+            raise DsortError(f"topk: k = {k} outside 0..{keys.size}")
+        out = np.empty(k, keys.dtype)
+        idx = np.empty(k, np.uint32)
+        self.check(self.lib.dsort_topk_keys(self.h, _ptr(keys), keys.size, k, KEY_TYPES[name],
+                                            ORDER_DESCENDING if descending else 0, _ptr(out), _ptr(idx)))
+        return out, idx
+
+    def sample_topk_dev(self, keys, first, k, descending=False, key_type=None, keys_out=None, idx_out=None):
+        """The global top-k over the communicator (dsort_sample_topk_dev_keys; collective): `keys`
+        is this rank's chunk, holding the global positions first .. first + len(keys) - 1.  Every
+        rank gets the same (keys, idx) of k elements, idx holding GLOBAL positions as uint32 bit
+        patterns; the arguments as for topk_dev."""
+        name, _ = self._tkey(keys, key_type, descending)
+        n = self._keys1d(keys, "keys").numel()
+        keys_out, idx_out = self._topk_outs(keys, k, keys_out, idx_out)
+        self.check(self.lib.dsort_sample_topk_dev_keys(self.h, keys.data_ptr() if n else None, n, int(first), k,
+                                                       KEY_TYPES[name], ORDER_DESCENDING if descending else 0,
+                                                       keys_out.data_ptr() if keys_out is not None and k else None,
+                                                       idx_out.data_ptr() if k else None, self._stream()))
+        return keys_out, idx_out
 
     def gen_uniform(self, t, seed, first=0):
         sfx = self._tsfx(t)

@@ -194,6 +194,9 @@ int dsort_synchronize(dsort_ctx *ctx);
                                          slice-length all-gather, 3 key gather, 4 second sort, 5 final
                                          gather); a leg the call never reaches is ignored.  -1 = off
                                          (default)                                                   */
+#define DSORT_OPT_TOPK_PATH 19         /* an ABI 10 addition: the path of dsort_topk_dev_keys / dsort_topk_keys:
+                                         -1 = dsort_plan_topk's rule (default), 0 = always the full
+                                         argsort, 1 = always the select path (tests, A/B)            */
 int dsort_set_option(dsort_ctx *ctx, int option, int64_t value);
 int dsort_get_option(const dsort_ctx *ctx, int option, int64_t *value);
 
@@ -596,6 +599,77 @@ int dsort_sample_sort_dev_keys(dsort_ctx *ctx, const void *d_keys, size_t n_loca
 int dsort_sample_argsort_dev_keys(dsort_ctx *ctx, const void *d_keys, size_t n_local, uint64_t first,
                                   int key_type, int flags, void **d_keys_out, uint32_t **d_idx_out,
                                   size_t *n_out, void *stream);
+
+/* ---------------------------------------------------------------- top-k ----------------
+ * An ABI 10 addition (new symbols and option 19; no struct, existing option or call changes): the
+ * first k entries of the stable argsort in the typed order, without sorting the other n - k keys.
+ *
+ * Contract.  d_idx_out[j], j < k, is exactly what dsort_argsort_dev_keys of the same keys, key_type
+ * and flags returns in position j, and d_keys_out[j] its key, bit for bit: the output is sorted
+ * (DSORT_ORDER_DESCENDING: the k largest, largest first); keys of equal bits come in ascending
+ * position, and where the cut falls inside a run of equal keys the lowest positions win; floats in
+ * totalOrder, with the rules on NaN and -0.0 of "Key types and order".
+ *
+ * Local calls.  d_keys_out (k keys) may be NULL, d_idx_out (k positions) is required; both are
+ * caller-owned and must not overlap d_keys, which is not modified.  Exactly k elements of each
+ * output are written.  DSORT_EINVAL before any memory is touched: a NULL ctx (plain return), an
+ * unknown key_type or flag bit, k > n, n > 2^32, a NULL pointer whose count is non-zero.  k == 0
+ * touches nothing.  Asynchronous on `stream` under the argsort's stream rules (with an 8-byte type
+ * and DSORT_OPT_ARGSORT_WIDE = 0 the inner argsort's one host wait for min/max remains).
+ * dsort_get_stats afterwards shows the inner sort's statistics: keys_in == k on the select path, n
+ * on the full path; the fault-injection options act inside the inner sort as when it is called
+ * directly.
+ *
+ * The select path (csrc/dsort_topk.hip).  With w the codec's word of a key, a radix select on
+ * u = w ^ sign_bit, most significant digit first, digits of 11 bits: 3 histogram passes over the
+ * keys for 4-byte types, 6 for 8-byte types (dsort_plan_topk's `digits`), each counting only the
+ * keys whose higher digits equal the prefix chosen so far; the prefix lives on the device and
+ * nothing waits on the host.  After the last pass the prefix is the threshold T; one more read of
+ * the keys writes the k winners -- u < T, and the first k_rest copies of T -- in ascending
+ * position, and these are sorted: 4-byte keys as the pair sort's packed words by the int64 sort, 8-
+ * byte keys by the int64 argsort of the k candidate keys and a gather of their positions.
+ * Memory (context arenas, grow-only): 16 MiB of histogram rows (2048 workgroups x 2048 bins; fewer
+ * workgroups below 2^23 keys) and 0.3 MiB of tables, plus 8 k bytes (4-byte keys: the pair arena) or
+ * 16 k bytes (8-byte keys: candidates, positions and their order), on top of the inner sort's memory
+ * for k keys.
+ * The full path is dsort_argsort_dev_keys into context arenas (4 n bytes of indices, and n keys
+ * when d_keys_out is given) and a copy of the first k.
+ *
+ * dsort_plan_topk, the host rule: *path = 0 nothing to do (k == 0), 1 the select path, 2 the full
+ * argsort and its first k; topk_path_opt is DSORT_OPT_TOPK_PATH's value: 0 and 1 force a path, -1
+ * takes the full argsort below 2^24 keys and when k > n / 2 (where the two paths were measured to
+ * cross with a margin; below 2^24 keys a small k is still faster through the select path, which
+ * the option forces).  *digits = the histogram
+ * passes of the select path for the width.  Either output may be NULL.  DSORT_EINVAL: key_bytes not
+ * 4 or 8, n > 2^32, k > n, an option value outside -1..1.
+ *
+ * Across ranks: dsort_sample_topk_dev_keys is collective.  Every rank passes its chunk, holding the
+ * global positions first .. first + n_local - 1, and receives the same global top-k -- k keys
+ * (d_keys_out, may be NULL) and their GLOBAL positions (d_idx_out) -- in caller-owned memory.  A
+ * rank with n_local == 0 (d_keys may be NULL) still joins.  One exchange call:
+ *   collective 0   all-gather of every rank's (first, n_local, k, key_type, flags);
+ *   collective 1   all-to-all-v of the candidates: every rank selects its own min(k, n_local)
+ *                  winners with the select path above (positions offset by `first`) and sends the
+ *                  same block to every rank; the counts follow from the table.  4-byte keys travel as
+ *                  packed words; 8-byte keys as their keys (collective 1) and their positions
+ *                  (collective 2) -- the numbering of DSORT_OPT_TEST_FAIL_EXCHANGE.
+ * The blocks land in the order of the ranges' starts, not of the ranks, so that equal keys are in
+ * ascending global position; every rank then sorts the candidates as the local call does and takes
+ * the first k.  Checked symmetrically after collective 0 -- DSORT_EINVAL on every rank from the same
+ * call, the communicator stays usable: ranks that disagree on k, key_type or flags, overlapping
+ * ranges (dsort_plan_gather_table's rule), k above the total key count, more than 256 ranks,
+ * nranks * k >= 2^32.  Before any collective: the local calls' argument checks, and
+ * first + n_local > 2^32.  Gates, deadline, dsort_comm_abort and DSORT_OPT_TEST_FAIL_EXCHANGE work as
+ * in a gather; the kill options do not act on it; DSORT_OPT_TOPK_PATH does not either (a rank's
+ * candidates always come from the select path).  The RCCL path has run with one rank only. */
+int dsort_plan_topk(size_t n, size_t k, int key_bytes, int topk_path_opt, int *path, int *digits);
+int dsort_topk_dev_keys(dsort_ctx *ctx, const void *d_keys, size_t n, size_t k, int key_type, int flags,
+                        void *d_keys_out, uint32_t *d_idx_out, void *stream);
+/* host form (synchronous, staged like dsort_argsort_keys) */
+int dsort_topk_keys(dsort_ctx *ctx, const void *keys, size_t n, size_t k, int key_type, int flags,
+                    void *keys_out, uint32_t *idx);
+int dsort_sample_topk_dev_keys(dsort_ctx *ctx, const void *d_keys, size_t n_local, uint64_t first, size_t k,
+                               int key_type, int flags, void *d_keys_out, uint32_t *d_idx_out, void *stream);
 
 /* ABI 9: the distributed record gather -- payloads follow their keys across ranks.
  *   d_dst[j] = the record at GLOBAL position d_idx[j], j < n_idx, wherever it lives.

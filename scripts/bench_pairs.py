@@ -62,6 +62,16 @@ decode kernel alone for 4- and 8-byte keys (float, descending), each as a ratio 
 copy of the same bytes in the same run, and sort_dev of 2^30 float32 keys beside the int32 sort_dev
 of the same bits and torch.sort of the same tensor.
 
+    python scripts/bench_pairs.py --topk [--log2 28] [--steps 10] [--out profiles/topk_bench.json]
+
+--topk times top-k selection (dsort_topk_dev_keys, keys and indices) at every --log2 size (default
+2^28): uniform float32 bits descending, int32 keys of [1, 100], all-equal int32 keys and uniform
+float64 bits, for k in 1, 64, 2^10, 2^16, 2^20 and n / 8, with the select path and the full path
+forced in turn in the same process (their results compared), torch.topk of the same tensor for
+context, and the path dsort_plan_topk takes; all six key types at k = 1024; and each histogram
+pass and the compaction of the select against a device-to-device copy of half the bytes it reads
+(the same traffic).
+
 Writes the JSON file and prints one summary line.  No GPU: fails (there is nothing to measure).
 """
 import argparse
@@ -586,6 +596,105 @@ def bench_keys_only(torch, dsort, ctx, lg, steps, warmup):
     return res
 
 
+def bench_topk(torch, dsort, ctx, n, steps, warmup):
+    """--topk at n keys: both forced paths per shape and k, torch.topk for context, the select's legs
+    against a copy of the same traffic."""
+    r4 = lambda x: round(x, 4)  # noqa: E731
+    lib = ctx.lib
+    lib.dsort_topk_leg_timing.restype = ctypes.c_int
+    lib.dsort_topk_leg_timing.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    lib.dsort_topk_leg_ms.restype = ctypes.c_int
+    lib.dsort_topk_leg_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
+                                      ctypes.POINTER(ctypes.c_double)]
+    res = {"n": n, "shapes": {}, "six_types_k1024": {}, "crossover": {}}
+
+    def one(keys, k, desc, key_type=None, with_torch=True):
+        W = keys.element_size()
+        ko = [torch.empty(k, dtype=keys.dtype, device="cuda") for _ in range(2)]
+        io = [torch.empty(k, dtype=torch.int32, device="cuda") for _ in range(2)]
+        e = {"k": k, "auto_path": dsort.plan_topk(keys.numel(), k, W)[0]}
+        for j, (label, path) in enumerate((("select", 1), ("full", 0))):
+            with ctx.options(topk_path=path):
+                runs = [timed(torch, lambda: ctx.topk_dev(keys, k, descending=desc, key_type=key_type, keys_out=ko[j],
+                                                          idx_out=io[j]), steps, warmup) for _ in range(3)]
+            e[label + "_ms"] = r4(statistics.median(runs))
+            e[label + "_runs_ms"] = [r4(v) for v in runs]
+        e["select_over_full"] = r4(e["select_ms"] / e["full_ms"])
+        e["paths_agree"] = bool(torch.equal(io[0], io[1])) and bool(torch.equal(ko[0].view(torch.uint8), ko[1].view(torch.uint8)))
+        if with_torch:
+            try:
+                e["torch_topk_ms"] = r4(timed(torch, lambda: torch.topk(keys, k, largest=desc, sorted=True),
+                                              max(2, steps // 2), 1))
+            except Exception as ex:  # (a dtype or size torch.topk does not take)
+                e["torch_topk_ms"] = None
+                e["torch_topk_error"] = str(ex)[:120]
+            torch.cuda.empty_cache()
+        return e
+
+    def legs(keys, k, desc, key_type=None):
+        """One select with the leg events on: each histogram pass and the compaction against a
+        device-to-device copy of half the bytes it reads."""
+        W = keys.element_size()
+        half = torch.empty(n * W // 2, dtype=torch.uint8, device="cuda")
+        dst = torch.empty_like(half)
+        copy_ms = timed(torch, lambda: dst.copy_(half), steps, warmup)
+        del half, dst
+        torch.cuda.empty_cache()
+        ctx.check(lib.dsort_topk_leg_timing(ctx.h, 1))
+        hist, comp = [], []
+        with ctx.options(topk_path=1):
+            for _ in range(warmup + steps):
+                ctx.topk_dev(keys, k, descending=desc, key_type=key_type)
+                h = (ctypes.c_double * 6)()
+                p, c = ctypes.c_int(), ctypes.c_double()
+                ctx.check(lib.dsort_topk_leg_ms(ctx.h, h, ctypes.byref(p), ctypes.byref(c)))
+                hist.append([h[i] for i in range(p.value)])
+                comp.append(c.value)
+        ctx.check(lib.dsort_topk_leg_timing(ctx.h, 0))
+        hist, comp = hist[warmup:], comp[warmup:]
+        hm = [statistics.median(col) for col in zip(*hist)]
+        cm = statistics.median(comp)
+        return {"k": k, "bytes_read_per_leg": n * W, "memcpy_of_half_ms": r4(copy_ms), "hist_ms": [r4(v) for v in hm],
+                "hist_over_memcpy": [r4(v / copy_ms) for v in hm], "compact_ms": r4(cm),
+                "compact_over_memcpy": r4(cm / copy_ms)}
+
+    ks = [1, 64, 1 << 10, 1 << 16, 1 << 20, n // 8]
+    bits32 = torch.empty(n, dtype=torch.int32, device="cuda")
+    ctx.gen_uniform(bits32, 0x5EED2026, 0)
+    shapes = [("f32_uniform_bits_desc", lambda: bits32.view(torch.float32), True),
+              ("i32_1_to_100_asc", lambda: torch.randint(1, 101, (n,), dtype=torch.int32, device="cuda"), False),
+              ("i32_all_equal_asc", lambda: torch.full((n,), 42, dtype=torch.int32, device="cuda"), False)]
+    for label, make, desc in shapes:
+        keys = make()
+        res["shapes"][label] = {"by_k": [one(keys, k, desc) for k in ks], "legs": legs(keys, 1 << 10, desc)}
+        del keys
+        torch.cuda.empty_cache()
+    for name in ("i32", "u32", "f32"):
+        keys = bits32.view(torch.float32) if name == "f32" else bits32
+        res["six_types_k1024"][name] = one(keys, 1 << 10, True, key_type=name, with_torch=False)
+    del bits32
+    torch.cuda.empty_cache()
+    bits64 = torch.empty(n, dtype=torch.int64, device="cuda")
+    ctx.gen_uniform(bits64, 0x5EED2026, 0)
+    f64 = bits64.view(torch.float64)
+    res["shapes"]["f64_uniform_bits_asc"] = {"by_k": [one(f64, k, False) for k in ks], "legs": legs(f64, 1 << 10, False)}
+    for name in ("i64", "u64", "f64"):
+        keys = f64 if name == "f64" else bits64
+        res["six_types_k1024"][name] = one(keys, 1 << 10, True, key_type=name, with_torch=False)
+    # where the two paths cross (dsort_plan_topk's constants): large k at n keys, and small inputs
+    f32 = bits64.view(torch.float32)[:n]
+    fracs = [(1, 4), (3, 8), (1, 2), (5, 8), (3, 4), (1, 1)]
+    small = [1 << lg for lg in (10, 12, 14, 16, 18, 20, 22, 24, 26) if (1 << lg) < n]
+    for label, keys, desc in (("f32_uniform_bits_desc", f32, True), ("f64_uniform_bits_asc", f64, False)):
+        res["crossover"][label] = {
+            "large_k": [{"k_over_n": f"{a}/{b}", **one(keys, n // b * a, desc, with_torch=False)} for a, b in fracs],
+            "small_n": [{"n": m, "k_1": one(keys[:m], 1, desc, with_torch=False),
+                         "k_n_over_64": one(keys[:m], m // 64, desc, with_torch=False),
+                         "k_n_over_8": one(keys[:m], m // 8, desc, with_torch=False),
+                         "k_n_over_2": one(keys[:m], m // 2, desc, with_torch=False)} for m in small]}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2", type=int, nargs="+", default=None)
@@ -607,13 +716,19 @@ def main():
                     help="time typed keys: argsort_dev of float32 / float64 keys, ascending and descending, beside the "
                          "integer argsort of the same bits (default 2^28 keys), and the keys-only path's encode and "
                          "decode kernels and float32 sort_dev at 2^28 and 2^30 (profiles/pairs_typed_bench.json)")
+    ap.add_argument("--topk", action="store_true",
+                    help="time top-k selection: the select path and the full argsort path forced in turn, torch.topk "
+                         "for context, the select's passes against a copy of the same traffic (default 2^28 keys, "
+                         "profiles/topk_bench.json)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    args.log2 = args.log2 or ([28] if args.sample or args.gather or args.sample_i64 or args.typed else [28, 30])
+    args.log2 = args.log2 or ([28] if args.sample or args.gather or args.sample_i64 or args.typed or args.topk
+                              else [28, 30])
     name = "pairs_gather_bench.json" if args.gather else "pairs_sample_bench.json" if args.sample else "pairs_bench.json"
     name = "pairs_i64_bench.json" if args.i64 else name
     name = "pairs_sample_i64_bench.json" if args.sample_i64 else name
     name = "pairs_typed_bench.json" if args.typed else name
+    name = "topk_bench.json" if args.topk else name
     args.out = args.out or os.path.join(REPO, "profiles", name)
 
     import torch
@@ -623,6 +738,37 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_pairs: no GPU visible (nothing is measured without one)")
     ctx = dsort.Context(0)
+    if args.topk:
+        res = {"what": "top-k selection (dsort.h, top-k), keys resident in HBM: dsort_topk_dev_keys (k keys and "
+                       "indices) with the select path and the full argsort path forced in turn in one process, ms per "
+                       "call of --steps back-to-back calls (median of 3 such runs, all listed), torch.topk(sorted=True) "
+                       "of the same tensor for context; legs: each histogram pass and the compaction of the select "
+                       "(HIP events around the kernel, median) against a device-to-device copy of half the bytes it "
+                       "reads",
+               "device": torch.cuda.get_device_name(0), "steps": args.steps, "warmup": args.warmup,
+               "sizes": [bench_topk(torch, dsort, ctx, 1 << lg, args.steps, args.warmup) for lg in args.log2]}
+        ctx.close()
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print(json.dumps({"topk_bench": [
+            {"n": s["n"],
+             **{lb: {"k": [e["k"] for e in v["by_k"]], "select_ms": [e["select_ms"] for e in v["by_k"]],
+                     "full_ms": [e["full_ms"] for e in v["by_k"]],
+                     "torch_topk_ms": [e.get("torch_topk_ms") for e in v["by_k"]],
+                     "agree": all(e["paths_agree"] for e in v["by_k"]),
+                     "hist_over_memcpy": v["legs"]["hist_over_memcpy"],
+                     "compact_over_memcpy": v["legs"]["compact_over_memcpy"]} for lb, v in s["shapes"].items()},
+             "six_types_k1024": {t: [e["select_ms"], e["full_ms"], e["paths_agree"]]
+                                 for t, e in s["six_types_k1024"].items()},
+             "crossover": {lb: {"large_k": [[e["k_over_n"], e["select_ms"], e["full_ms"]] for e in v["large_k"]],
+                                "small_n": [[e["n"]] + [e[c][p] for c in ("k_1", "k_n_over_64", "k_n_over_8",
+                                                                          "k_n_over_2")
+                                                        for p in ("select_ms", "full_ms")]
+                                            for e in v["small_n"]]} for lb, v in s["crossover"].items()}}
+            for s in res["sizes"]]}), flush=True)
+        return
     if args.typed:
         res = {"what": "typed keys (dsort.h, Key types and order), resident in HBM.  fused: argsort_dev (sorted keys and "
                        "indices) of float keys, ascending and descending, beside the integer argsort_dev of the same "
