@@ -18,9 +18,9 @@
 
 #include "dsort_exch.h"
 
-#define DSORT_VERSION_STRING "libdsort 0.1 (gfx950, HIP " DSORT_STR(HIP_VERSION_MAJOR) "." DSORT_STR(HIP_VERSION_MINOR) ")"
 #define DSORT_STR2(x) #x
 #define DSORT_STR(x) DSORT_STR2(x)
+#define DSORT_VERSION_STRING "libdsort 0.1 (gfx950, HIP " DSORT_STR(HIP_VERSION_MAJOR) "." DSORT_STR(HIP_VERSION_MINOR) ")"
 
 namespace dsort {
 
@@ -35,9 +35,9 @@ int hip_err(dsort_ctx *ctx, hipError_t e, const char *what) {
     return set_err(ctx, code, m);
 }
 
-int ensure(dsort_ctx *ctx, void **buf, size_t *have, size_t need, const char *what) {
-    if (need <= *have && *buf) return DSORT_OK;
-    if (*buf) {
+int ensure(dsort_ctx *ctx, DevBuf &buf, size_t need, const char *what) {
+    if (need <= buf.bytes && buf.p) return DSORT_OK;
+    if (buf.p) {
         // the old arena may still be used by queued work on any stream of this device.  Inside the
         // bucket exchange's second level (ctx->poll_waits) the keys are still in flight on the comm
         // stream, which a dead peer never completes: a device-wide synchronize would hang there, so
@@ -52,38 +52,38 @@ int ensure(dsort_ctx *ctx, void **buf, size_t *have, size_t need, const char *wh
             hipError_t e = hipDeviceSynchronize();
             if (e != hipSuccess) return hip_err(ctx, e, "hipDeviceSynchronize (arena grow)");
         }
-        release_dev(ctx, *buf);
-        *buf = nullptr;
-        *have = 0;
+        release_dev(ctx, buf);
     }
     size_t sz = need < 256 ? 256 : need;
-    hipError_t e = hipMalloc(buf, sz);
+    hipError_t e = hipMalloc(&buf.p, sz);
     if (e != hipSuccess) {
-        *buf = nullptr;
+        buf.p = nullptr;
         return set_err(ctx, DSORT_ENOMEM, std::string("hipMalloc failed for ") + what + " (" +
                                               std::to_string(sz) + " bytes): " + hipGetErrorString(e));
     }
-    *have = sz;
+    buf.bytes = sz;
     return DSORT_OK;
 }
 
-void release_dev(dsort_ctx *ctx, void *p) {
-    if (!p) return;
-    if (ctx->poll_waits) {
-        ctx->dev_later.push_back(p);
+void release_dev(dsort_ctx *ctx, DevBuf &buf) {
+    if (buf.p && ctx->poll_waits) {
+        ctx->dev_later.push_back(buf.p);
         ++ctx->deferred_n;
-    } else {
-        (void)hipFree(p);
+    } else if (buf.p) {
+        (void)hipFree(buf.p);
     }
+    buf.p = nullptr;
+    buf.bytes = 0;
 }
-void release_host(dsort_ctx *ctx, void *p) {
-    if (!p) return;
-    if (ctx->poll_waits) {
-        ctx->host_later.push_back(p);
+void release_host(dsort_ctx *ctx, HostBuf &buf) {
+    if (buf.p && ctx->poll_waits) {
+        ctx->host_later.push_back(buf.p);
         ++ctx->deferred_n;
-    } else {
-        (void)hipHostFree(p);
+    } else if (buf.p) {
+        (void)hipHostFree(buf.p);
     }
+    buf.p = nullptr;
+    buf.bytes = 0;
 }
 void flush_later(dsort_ctx *ctx) {
     for (void *p : ctx->dev_later) (void)hipFree(p);
@@ -93,27 +93,25 @@ void flush_later(dsort_ctx *ctx) {
 }
 
 // grow-only pinned host buffer
-int ensure_host(dsort_ctx *ctx, void **buf, size_t *have, size_t need) {
-    if (need <= *have && *buf) return DSORT_OK;
-    if (*buf) release_host(ctx, *buf);
-    *buf = nullptr;
-    *have = 0;
-    if (hipHostMalloc(buf, need, hipHostMallocDefault) != hipSuccess) {
-        *buf = nullptr;
+int ensure_host(dsort_ctx *ctx, HostBuf &buf, size_t need) {
+    if (need <= buf.bytes && buf.p) return DSORT_OK;
+    release_host(ctx, buf);
+    if (hipHostMalloc(&buf.p, need, hipHostMallocDefault) != hipSuccess) {
+        buf.p = nullptr;
         return set_err(ctx, DSORT_ENOMEM, "hipHostMalloc failed (" + std::to_string(need) + " bytes)");
     }
-    *have = need;
+    buf.bytes = need;
     return DSORT_OK;
 }
 
-// the pinned mirror of ctx->small (grow-only; never replaced while keys are in flight)
-int ensure_small_host(dsort_ctx *ctx, size_t need) {
-    if (ctx->small_host_bytes >= need) return DSORT_OK;
-    if (ctx->small_host) (void)hipHostFree(ctx->small_host);
-    ctx->small_host = nullptr;
-    ctx->small_host_bytes = 0;
-    DSORT_HIP(ctx, hipHostMalloc(&ctx->small_host, need, hipHostMallocDefault));
-    ctx->small_host_bytes = need;
+int LegClock::wait_last(dsort_ctx *ctx) const {
+    DSORT_HIP(ctx, hipEventSynchronize(ev[n - 1]));
+    return DSORT_OK;
+}
+int LegClock::elapsed(dsort_ctx *ctx, int a, int b, double *ms) const {
+    float f = 0;
+    DSORT_HIP(ctx, hipEventElapsedTime(&f, ev[a], ev[b]));
+    *ms = f;
     return DSORT_OK;
 }
 
@@ -223,9 +221,9 @@ static int fingerprint_t(dsort_ctx *ctx, const T *d, size_t n, uint64_t *sum, ui
                          uint64_t *desc, bool want_desc) {
     if (!ctx) return DSORT_EINVAL;
     hipStream_t s = ctx->stream;
-    DSORT_HIP(ctx, hipMemsetAsync(ctx->red, 0, 64, s));
+    DSORT_HIP(ctx, hipMemsetAsync(ctx->red.p, 0, 64, s));
     if (n) {
-        auto *red = static_cast<unsigned long long *>(ctx->red);
+        auto *red = ctx->red.as<unsigned long long>();
         if (!want_desc) {
             if (int rc = fingerprint_launch<T>(ctx, d, n, red, s)) return rc;
         } else {
@@ -233,11 +231,12 @@ static int fingerprint_t(dsort_ctx *ctx, const T *d, size_t n, uint64_t *sum, ui
             DSORT_HIP(ctx, hipGetLastError());
         }
     }
-    DSORT_HIP(ctx, hipMemcpyAsync(ctx->red_host, ctx->red, 64, hipMemcpyDeviceToHost, s));
+    const uint64_t *h = ctx->red_host.as<uint64_t>();
+    DSORT_HIP(ctx, hipMemcpyAsync(ctx->red_host.p, ctx->red.p, 64, hipMemcpyDeviceToHost, s));
     DSORT_HIP(ctx, hipStreamSynchronize(s));
-    if (sum) *sum = ctx->red_host[0];
-    if (xr) *xr = ctx->red_host[1];
-    if (desc) *desc = ctx->red_host[2];
+    if (sum) *sum = h[0];
+    if (xr) *xr = h[1];
+    if (desc) *desc = h[2];
     return DSORT_OK;
 }
 
@@ -246,10 +245,10 @@ template <typename T>
 static int sort_host(dsort_ctx *ctx, T *host, size_t n) {
     if (!ctx || (!host && n)) return set_err(ctx, DSORT_EINVAL, "null argument");
     if (n < 2) return DSORT_OK;
-    int rc = ensure(ctx, &ctx->io, &ctx->io_bytes, n * sizeof(T), "staging");
+    int rc = ensure(ctx, ctx->io, n * sizeof(T), "staging");
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    T *d = static_cast<T *>(ctx->io);
+    T *d = ctx->io.as<T>();
     DSORT_HIP(ctx, hipMemcpyAsync(d, host, n * sizeof(T), hipMemcpyHostToDevice, s));
     rc = sort_device<T>(ctx, d, d, n, s, true);
     if (rc) return rc;
@@ -268,12 +267,12 @@ static int merge_host(dsort_ctx *ctx, const T *const runs[], const size_t lens[]
     }
     if (n == 0) return DSORT_OK;
     if (!out) return set_err(ctx, DSORT_EINVAL, "null output");
-    int rc = ensure(ctx, &ctx->io, &ctx->io_bytes, n * sizeof(T), "staging");
+    int rc = ensure(ctx, ctx->io, n * sizeof(T), "staging");
     if (rc) return rc;
-    rc = ensure(ctx, &ctx->io2, &ctx->io2_bytes, n * sizeof(T), "staging 2");
+    rc = ensure(ctx, ctx->io2, n * sizeof(T), "staging 2");
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    T *din = static_cast<T *>(ctx->io), *dout = static_cast<T *>(ctx->io2);
+    T *din = ctx->io.as<T>(), *dout = ctx->io2.as<T>();
     size_t off = 0;
     for (int j = 0; j < k; ++j) {
         if (lens[j])
@@ -363,20 +362,19 @@ int dsort_init(dsort_ctx **out, int device) {
     if (!ctx) return DSORT_ENOMEM;
     ctx->device = device;
     if (hipSetDevice(device) != hipSuccess ||
-        hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
+        hipStreamCreateWithFlags(&ctx->stream.h, hipStreamNonBlocking) != hipSuccess) {
         delete ctx;
         return DSORT_EHIP;
     }
-    if (hipMalloc(&ctx->red, 64) != hipSuccess ||
-        hipHostMalloc((void **)&ctx->red_host, 64, hipHostMallocDefault) != hipSuccess) {
+    if (ensure(ctx, ctx->red, 64, "reduction accumulators") || ensure_host(ctx, ctx->red_host, 64)) {
         dsort_finalize(ctx);
         return DSORT_ENOMEM;
     }
     ctx->ev_ok = true;
     for (auto &e : ctx->ev)
-        if (hipEventCreate(&e) != hipSuccess) ctx->ev_ok = false;
+        if (hipEventCreate(&e.h) != hipSuccess) ctx->ev_ok = false;
     for (auto &e : ctx->kev)
-        if (hipEventCreate(&e) != hipSuccess) ctx->ev_ok = false;
+        if (hipEventCreate(&e.h) != hipSuccess) ctx->ev_ok = false;
     ctx->ev_created = ctx->ev_ok;
     *out = ctx;
     return DSORT_OK;
@@ -392,51 +390,7 @@ int dsort_finalize(dsort_ctx *ctx) {
     }
     ctx->poll_waits = false;
     flush_later(ctx);
-    void *bufs[] = {ctx->scratch, ctx->scratch2, ctx->splits, ctx->groups, ctx->io, ctx->io2, ctx->red,
-                    ctx->local, ctx->recv, ctx->recv2, ctx->small, ctx->text_status,
-                    ctx->bucket, ctx->sub, ctx->sub_alt, ctx->stmp, ctx->bxs, ctx->tfb, ctx->fence, ctx->pairs,
-                    ctx->spairs_k, ctx->spairs_v, ctx->gat_req, ctx->gat_rreq, ctx->gat_rep, ctx->gat_back,
-                    ctx->gat_small, ctx->a64_b, ctx->a64_idx, ctx->a64_part, ctx->s64_k, ctx->s64_i,
-                    ctx->s64_sa, ctx->s64_pos, ctx->s64_got, ctx->kenc, ctx->tk_rows, ctx->tk_small,
-                    ctx->tk_ck, ctx->tk_cp, ctx->tk_rk, ctx->tk_rp, ctx->tk_sk};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    if (ctx->red_host) (void)hipHostFree(ctx->red_host);
-    if (ctx->small_host) (void)hipHostFree(ctx->small_host);
-    if (ctx->gat_host) (void)hipHostFree(ctx->gat_host);
-    for (auto &e : ctx->gat_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (ctx->xfer) (void)hipHostFree(ctx->xfer);
-    if (ctx->xfer2) (void)hipHostFree(ctx->xfer2);
-    if (ctx->fence_host) (void)hipHostFree(ctx->fence_host);
-    if (ctx->groups_host) (void)hipHostFree(ctx->groups_host);
-    if (ctx->groups_ev) (void)hipEventDestroy(ctx->groups_ev);
-    if (ctx->bucket_host) (void)hipHostFree(ctx->bucket_host);
-    if (ctx->bucket_ev) (void)hipEventDestroy(ctx->bucket_ev);
-    if (ctx->sub_host) (void)hipHostFree(ctx->sub_host);
-    if (ctx->sub_ev) (void)hipEventDestroy(ctx->sub_ev);
-    if (ctx->side_ev) (void)hipEventDestroy(ctx->side_ev);
-    if (ctx->ready_ev) (void)hipEventDestroy(ctx->ready_ev);
-    if (ctx->side) (void)hipStreamDestroy(ctx->side);
-    for (auto &e : ctx->xev)
-        if (e) (void)hipEventDestroy(e);
-    if (ctx->xs) (void)hipStreamDestroy(ctx->xs);
-    if (ctx->done_ev) (void)hipEventDestroy(ctx->done_ev);
-    for (auto &e : ctx->pairs_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : ctx->a64_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : ctx->s64_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : ctx->tk_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (ctx->a64_mm_ev) (void)hipEventDestroy(ctx->a64_mm_ev);
-    for (auto &e : ctx->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto &e : ctx->kev)
-        if (e) (void)hipEventDestroy(e);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;  // (its arenas, events and streams free themselves: dsort_internal.h)
     return DSORT_OK;
 }
 
@@ -557,7 +511,7 @@ int dsort_get_stats(const dsort_ctx *cctx, dsort_stats *out) {
     if (!ctx->ev_ok) return DSORT_OK;
     if (hipStreamSynchronize(ctx->last_stream) != hipSuccess) return DSORT_EHIP;
     float ms = 0;
-    auto el = [&](int a, int b) -> double {
+    auto el = [&](StageEv a, StageEv b) -> double {
         if (!(ctx->ev_mask & (1u << a)) || !(ctx->ev_mask & (1u << b))) return 0.0;
         return hipEventElapsedTime(&ms, ctx->ev[a], ctx->ev[b]) == hipSuccess ? (double)ms : 0.0;
     };
@@ -570,21 +524,21 @@ int dsort_get_stats(const dsort_ctx *cctx, dsort_stats *out) {
             out->merge_kernel_launches += 1;
         }
     }
-    out->block_sort_ms = el(0, 1);
-    out->merge_ms = el(1, 2);
-    // (the bucket exchange's first wave recorded its tile sort and second level at 22/23, 28/29)
-    out->tile_sort_kernel_ms = el(7, 8) + el(22, 23);
-    out->partition_ms = el(0, 7);
-    out->bucket_hist_ms = el(9, 10);
-    out->bucket_scatter_ms = el(11, 12);
-    out->sub_partition_ms = el(13, 14) + el(28, 29);
-    if (ctx->ev_mask & 16u) {
-        out->exchange_ms = el(2, 3);
-        out->final_merge_ms = el(3, 4);
-        out->total_ms = el(0, 4);
-        out->alltoall_ms = el(5, 6);
+    auto wave0 = [](StageEv e) { return StageEv(e + kWave0Offset); };  // (the bucket exchange's first wave)
+    out->block_sort_ms = el(kEvStart, kEvTileSortDone);
+    out->merge_ms = el(kEvTileSortDone, kEvLocalDone);
+    out->tile_sort_kernel_ms = el(kEvTile0, kEvTile1) + el(wave0(kEvTile0), wave0(kEvTile1));
+    out->partition_ms = el(kEvStart, kEvTile0);
+    out->bucket_hist_ms = el(kEvHist0, kEvHist1);
+    out->bucket_scatter_ms = el(kEvScatter0, kEvScatter1);
+    out->sub_partition_ms = el(kEvSub0, kEvSub1) + el(wave0(kEvSub0), wave0(kEvSub1));
+    if (ctx->ev_mask & (1u << kEvFinalDone)) {
+        out->exchange_ms = el(kEvLocalDone, kEvExchangeDone);
+        out->final_merge_ms = el(kEvExchangeDone, kEvFinalDone);
+        out->total_ms = el(kEvStart, kEvFinalDone);
+        out->alltoall_ms = el(kEvAllToAll0, kEvAllToAll1);
     } else {
-        out->total_ms = el(0, 2);
+        out->total_ms = el(kEvStart, kEvLocalDone);
     }
     return DSORT_OK;
 }

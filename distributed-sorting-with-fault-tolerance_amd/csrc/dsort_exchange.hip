@@ -93,14 +93,6 @@ int exch_wait(dsort_ctx *ctx, hipStream_t s, bool with_stream, double deadline, 
     }
 }
 
-// Stage event i of the call (dsort_ctx::ev), when stage timing is on.
-static int stage_event(dsort_ctx *ctx, int i, hipStream_t s) {
-    if (!ctx->ev_ok) return DSORT_OK;
-    DSORT_HIP(ctx, hipEventRecord(ctx->ev[i], s));
-    ctx->ev_mask |= 1u << i;
-    return DSORT_OK;
-}
-
 static void exchange_fault_point(dsort_ctx *ctx, int stage) {
     if (ctx->opt.kill_in_exchange == stage) raise(SIGKILL);
 }
@@ -137,10 +129,10 @@ int allgather_u64(dsort_ctx *ctx, const uint64_t *src, size_t count, uint64_t *o
         return host_allgather(ctx, src, out, count * 8, what);
     }
     const size_t bytes = count * 8 * (size_t)(P + 1);
-    int rc = ensure(ctx, &ctx->small, &ctx->small_bytes, bytes, "sample-sort small buffers");
+    int rc = ensure(ctx, ctx->small, bytes, "sample-sort small buffers");
     if (rc) return rc;
     if ((rc = ensure_small_host(ctx, bytes))) return rc;
-    uint64_t *d = static_cast<uint64_t *>(ctx->small), *h = static_cast<uint64_t *>(ctx->small_host);
+    uint64_t *d = ctx->small.as<uint64_t>(), *h = ctx->small_host.as<uint64_t>();
     memcpy(h, src, count * 8);
     DSORT_HIP(ctx, hipMemcpyAsync(d, h, count * 8, hipMemcpyHostToDevice, s));
     DSORT_NCCLNB(ctx, ncclAllGather(d, d + count, count, ncclUint64, ctx->comm, s));
@@ -173,11 +165,11 @@ int rccl_group(dsort_ctx *ctx, const A2av &a, hipStream_t s, double deadline, co
 int a2av_peers(dsort_ctx *ctx, const A2av &a, hipStream_t s, double deadline, const char *what, const char *staging) {
     if (!ctx->has_transport) return rccl_group(ctx, a, s, deadline, what);
     const int P = ctx->nranks;
-    int rc = ensure_host(ctx, &ctx->xfer, &ctx->xfer_bytes, (a.stotal ? a.stotal : 1) * a.unit);
+    int rc = ensure_host(ctx, ctx->xfer, (a.stotal ? a.stotal : 1) * a.unit);
     if (rc) return rc;
-    rc = ensure_host(ctx, &ctx->xfer2, &ctx->xfer2_bytes, (a.rtotal ? a.rtotal : 1) * a.unit);
+    rc = ensure_host(ctx, ctx->xfer2, (a.rtotal ? a.rtotal : 1) * a.unit);
     if (rc) return rc;
-    if (a.stotal) DSORT_HIP(ctx, hipMemcpyAsync(ctx->xfer, a.sbuf, a.stotal * a.unit, hipMemcpyDeviceToHost, s));
+    if (a.stotal) DSORT_HIP(ctx, hipMemcpyAsync(ctx->xfer.p, a.sbuf, a.stotal * a.unit, hipMemcpyDeviceToHost, s));
     rc = exch_wait(ctx, s, true, deadline, staging);
     if (rc) return rc;
     std::vector<size_t> sc(P), sd(P), rcn(P), rd(P);
@@ -187,9 +179,9 @@ int a2av_peers(dsort_ctx *ctx, const A2av &a, hipStream_t s, double deadline, co
         rcn[r] = a.rcnt[r] * a.unit;
         rd[r] = a.roff[r] * a.unit;
     }
-    rc = host_alltoallv(ctx, ctx->xfer, sc.data(), sd.data(), ctx->xfer2, rcn.data(), rd.data(), what);
+    rc = host_alltoallv(ctx, ctx->xfer.p, sc.data(), sd.data(), ctx->xfer2.p, rcn.data(), rd.data(), what);
     if (rc) return rc;
-    if (a.rtotal) DSORT_HIP(ctx, hipMemcpyAsync(a.rbuf, ctx->xfer2, a.rtotal * a.unit, hipMemcpyHostToDevice, s));
+    if (a.rtotal) DSORT_HIP(ctx, hipMemcpyAsync(a.rbuf, ctx->xfer2.p, a.rtotal * a.unit, hipMemcpyHostToDevice, s));
     return DSORT_OK;
 }
 
@@ -268,10 +260,10 @@ static int comm_stream(dsort_ctx *ctx) {
     // share its queue, and then nothing on it runs beside the sort's kernels)
     int lo = 0, hi = 0;
     if (!ctx->xs && (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess ||
-                     hipStreamCreateWithPriority(&ctx->xs, hipStreamNonBlocking, hi) != hipSuccess))
+                     hipStreamCreateWithPriority(&ctx->xs.h, hipStreamNonBlocking, hi) != hipSuccess))
         return set_err(ctx, DSORT_EHIP, "hipStreamCreate (comm stream)");
     for (auto &e : ctx->xev)
-        if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess)
+        if (!e && hipEventCreateWithFlags(&e.h, hipEventDisableTiming) != hipSuccess)
             return set_err(ctx, DSORT_EHIP, "hipEventCreate (comm stream)");
     return DSORT_OK;
 }
@@ -300,12 +292,12 @@ struct WaveFence {
     int prepare(dsort_ctx *ctx) {
         if (r.empty()) return DSORT_OK;
         const size_t bytes = r.size() * 4 * sizeof(unsigned long long);
-        int rc = ensure(ctx, &ctx->fence, &ctx->fence_bytes, bytes, "wave fence");
-        return rc ? rc : ensure_host(ctx, &ctx->fence_host, &ctx->fence_host_bytes, bytes);
+        int rc = ensure(ctx, ctx->fence, bytes, "wave fence");
+        return rc ? rc : ensure_host(ctx, ctx->fence_host, bytes);
     }
     // which = 0: before, 1: after
     int print(dsort_ctx *ctx, hipStream_t s, int which) {
-        auto *acc = static_cast<unsigned long long *>(ctx->fence) + (size_t)which * 2 * r.size();
+        auto *acc = ctx->fence.as<unsigned long long>() + (size_t)which * 2 * r.size();
         DSORT_HIP(ctx, hipMemsetAsync(acc, 0, r.size() * 2 * sizeof(unsigned long long), s));
         for (size_t i = 0; i < r.size(); ++i)
             if (int rc = fingerprint_launch<T>(ctx, r[i].p, r[i].n, acc + 2 * i, s)) return rc;
@@ -319,10 +311,10 @@ struct WaveFence {
         int rc = print(ctx, s, 1);
         if (rc) return rc;
         const size_t m = r.size() * 4;
-        DSORT_HIP(ctx, hipMemcpyAsync(ctx->fence_host, ctx->fence, m * sizeof(unsigned long long),
+        DSORT_HIP(ctx, hipMemcpyAsync(ctx->fence_host.p, ctx->fence.p, m * sizeof(unsigned long long),
                                       hipMemcpyDeviceToHost, s));
         if ((rc = exch_wait(ctx, s, true, deadline, "wave fence"))) return rc;
-        const auto *h = static_cast<const unsigned long long *>(ctx->fence_host);
+        const auto *h = ctx->fence_host.as<const unsigned long long>();
         const size_t R2 = 2 * r.size();
         for (size_t i = 0; i < r.size(); ++i)
             if (h[2 * i] != h[R2 + 2 * i] || h[2 * i + 1] != h[R2 + 2 * i + 1])
@@ -346,9 +338,9 @@ static int sample_sort_bx(dsort_ctx *ctx, const T *d_in, const BxPlan &pl, T **d
     const bool host_tx = ctx->has_transport;
     if (host_tx) ctx->tx->plan(2 + bx_waves(Bl));  // samples, bucket starts, the waves (dsort_tx.h)
     const size_t rec = (size_t)pl.s_max * sizeof(BxSample);
-    int rc = ensure(ctx, &ctx->bxs, &ctx->bxs_bytes, rec * (size_t)(P + 1), "bucket-exchange samples");
+    int rc = ensure(ctx, ctx->bxs, rec * (size_t)(P + 1), "bucket-exchange samples");
     if (rc) return rc;
-    BxSample *mine = static_cast<BxSample *>(ctx->bxs), *all = mine + pl.s_max;
+    BxSample *mine = ctx->bxs.as<BxSample>(), *all = mine + pl.s_max;
     // 1. samples, all-gathered
     if ((rc = bx_sample<T>(ctx, d_in, pl, mine, s))) return rc;
     if (!host_tx) {
@@ -356,9 +348,9 @@ static int sample_sort_bx(dsort_ctx *ctx, const T *d_in, const BxPlan &pl, T **d
         rc = exch_wait(ctx, s, false, deadline, "sample all-gather (enqueue)");
         if (rc) return rc;
     } else {
-        rc = ensure_host(ctx, &ctx->xfer, &ctx->xfer_bytes, rec * (size_t)(P + 1));
+        rc = ensure_host(ctx, ctx->xfer, rec * (size_t)(P + 1));
         if (rc) return rc;
-        char *hm = static_cast<char *>(ctx->xfer), *ha = hm + rec;
+        char *hm = ctx->xfer.as<char>(), *ha = hm + rec;
         DSORT_HIP(ctx, hipMemcpyAsync(hm, mine, rec, hipMemcpyDeviceToHost, s));
         rc = exch_wait(ctx, s, true, deadline, "samples");
         if (rc) return rc;
@@ -392,13 +384,13 @@ static int sample_sort_bx(dsort_ctx *ctx, const T *d_in, const BxPlan &pl, T **d
     const int W = L.W;
     const int *jb = L.jb;
     if (!L.behind) {
-        rc = ensure(ctx, &ctx->recv, &ctx->recv_bytes, (L.nrecv ? L.nrecv : 1) * sizeof(T) + 16, "receive buffer");
+        rc = ensure(ctx, ctx->recv, (L.nrecv ? L.nrecv : 1) * sizeof(T) + 16, "receive buffer");
         if (rc) return rc;
     }
-    rc = ensure(ctx, &ctx->recv2, &ctx->recv2_bytes, (L.nout ? L.nout : 1) * sizeof(T), "sorted slice");
+    rc = ensure(ctx, ctx->recv2, (L.nout ? L.nout : 1) * sizeof(T), "sorted slice");
     if (rc) return rc;
-    T *rb = L.behind ? part : static_cast<T *>(ctx->recv);  // (the second level's source)
-    T *outp = static_cast<T *>(ctx->recv2);
+    T *rb = L.behind ? part : ctx->recv.as<T>();  // (the second level's source)
+    T *outp = ctx->recv2.as<T>();
     exchange_fault_point(ctx, 2);
     // DSORT_OPT_TEST_WAVE_FENCE: what wave 1 still needs while wave 0's second level and tile sort
     // run -- its sends (part, every q != me), this rank's own wave-1 buckets (read in place when
@@ -420,7 +412,9 @@ static int sample_sort_bx(dsort_ctx *ctx, const T *d_in, const BxPlan &pl, T **d
     uint64_t out_off = 0;
     auto finish_wave = [&](int w) -> int {
         int rc = DSORT_OK;
-        if (w == 0 && ((rc = stage_event(ctx, 6, s)) || (rc = stage_event(ctx, 3, s)))) return rc;  // (its keys are in)
+        if (w == 0 &&  // (its keys are in)
+            ((rc = stage_event(ctx, s, true, kEvAllToAll1)) || (rc = stage_event(ctx, s, true, kEvExchangeDone))))
+            return rc;
         if (w == 0 && fence.on() && (rc = fence.print(ctx, s, 0))) return rc;
         uint64_t nw = 0;
         rc = bx_local_sort<T>(ctx, rb, outp, pl, hb_all.data(), L.hc_all.data(), L.base.data() + (size_t)w * P, jb[w],
@@ -431,7 +425,7 @@ static int sample_sort_bx(dsort_ctx *ctx, const T *d_in, const BxPlan &pl, T **d
     };
     // 4. the buckets to their ranks: per wave one send and one receive per peer (all-to-all-v over
     //    xGMI), on the comm stream after the partition
-    if ((rc = stage_event(ctx, 5, s))) return rc;
+    if ((rc = stage_event(ctx, s, true, kEvAllToAll0))) return rc;
     if (host_tx) {
         // The same order as RCCL's: wave w's send ranges are staged from `part` right
         // before its all-to-all, and wave w's second level and tile sort are queued before wave
@@ -440,9 +434,9 @@ static int sample_sort_bx(dsort_ctx *ctx, const T *d_in, const BxPlan &pl, T **d
         // (send displacements = positions in part); the receive layout is the device one minus
         // the partition (behind: the other sources from n_local on, this rank's own buckets not
         // shipped).
-        rc = ensure_host(ctx, &ctx->xfer, &ctx->xfer_bytes, (pl.n_local ? pl.n_local : 1) * sizeof(T));
+        rc = ensure_host(ctx, ctx->xfer, (pl.n_local ? pl.n_local : 1) * sizeof(T));
         if (rc) return rc;
-        rc = ensure_host(ctx, &ctx->xfer2, &ctx->xfer2_bytes, (L.nrecv ? L.nrecv : 1) * sizeof(T));
+        rc = ensure_host(ctx, ctx->xfer2, (L.nrecv ? L.nrecv : 1) * sizeof(T));
         if (rc) return rc;
         const uint64_t shift = L.behind ? pl.n_local : 0;
         for (int w = 0; w < W; ++w) {
@@ -456,7 +450,7 @@ static int sample_sort_bx(dsort_ctx *ctx, const T *d_in, const BxPlan &pl, T **d
                 rcn[q] = self ? 0 : L.rcnt[k] * sizeof(T);
                 rd[q] = self ? 0 : (L.rpos[k] - shift) * sizeof(T);
                 if (sc[q])  // (stage this wave's range for q, and nothing else)
-                    DSORT_HIP(ctx, hipMemcpyAsync(static_cast<char *>(ctx->xfer) + sd[q], part + L.soff[k], sc[q],
+                    DSORT_HIP(ctx, hipMemcpyAsync(ctx->xfer.as<char>() + sd[q], part + L.soff[k], sc[q],
                                                   hipMemcpyDeviceToHost, s));
                 if (!self && L.rcnt[k]) {
                     lo = std::min<uint64_t>(lo, L.rpos[k]);
@@ -465,11 +459,11 @@ static int sample_sort_bx(dsort_ctx *ctx, const T *d_in, const BxPlan &pl, T **d
             }
             rc = exch_wait(ctx, s, true, deadline, w ? "key staging (wave 1)" : "key staging (wave 0)");
             if (rc) return rc;
-            rc = host_alltoallv(ctx, ctx->xfer, sc.data(), sd.data(), ctx->xfer2, rcn.data(), rd.data(),
+            rc = host_alltoallv(ctx, ctx->xfer.p, sc.data(), sd.data(), ctx->xfer2.p, rcn.data(), rd.data(),
                                 w ? "key all-to-all (wave 1)" : "key all-to-all (wave 0)");
             if (rc) return rc;
             if (hi > lo)
-                DSORT_HIP(ctx, hipMemcpyAsync(rb + lo, static_cast<char *>(ctx->xfer2) + (lo - shift) * sizeof(T),
+                DSORT_HIP(ctx, hipMemcpyAsync(rb + lo, ctx->xfer2.as<char>() + (lo - shift) * sizeof(T),
                                               (hi - lo) * sizeof(T), hipMemcpyHostToDevice, s));
             if ((rc = finish_wave(w))) return rc;
         }
@@ -569,16 +563,14 @@ static int sample_sort(dsort_ctx *ctx, const T *d_in, size_t n_local, T **d_out,
         d_keys = d_in;
         ctx->ev_mask = 0;
         ctx->last_stream = s;
-        if (ctx->ev_ok) {
-            for (int e = 0; e < 3; ++e) DSORT_HIP(ctx, hipEventRecord(ctx->ev[e], s));
-            ctx->ev_mask = 7u;
-        }
+        for (int e = kEvStart; e <= kEvLocalDone; ++e)  // (no local sort: its three events at once)
+            if ((rc = stage_event(ctx, s, true, StageEv(e)))) return rc;
         st.keys_in = n_local;
     } else {
         // 1. local sort (the worker's merge_sort) into the context's local arena
-        rc = ensure(ctx, &ctx->local, &ctx->local_bytes, (n_local ? n_local : 1) * sizeof(T), "local run");
+        rc = ensure(ctx, ctx->local, (n_local ? n_local : 1) * sizeof(T), "local run");
         if (rc) return rc;
-        T *dk = static_cast<T *>(ctx->local);
+        T *dk = ctx->local.as<T>();
         rc = sort_device<T>(ctx, d_in, dk, n_local, s, true);
         if (rc) return rc;
         d_keys = dk;
@@ -595,11 +587,11 @@ static int sample_sort(dsort_ctx *ctx, const T *d_in, size_t n_local, T **d_out,
     const size_t off_cnt = off_cut + (size_t)(P + 1) * 8;         // 1 uint64 (n_local)
     // (and room for the count all-gather, P + P*P uint64 from 0 on: it never regrows the arenas)
     const size_t total_small = off_cnt + (size_t)P * 8 + (size_t)P * P * 8 + 64;
-    rc = ensure(ctx, &ctx->small, &ctx->small_bytes, total_small, "sample-sort small buffers");
+    rc = ensure(ctx, ctx->small, total_small, "sample-sort small buffers");
     if (rc) return rc;
     if ((rc = ensure_small_host(ctx, total_small))) return rc;
-    char *dsm = static_cast<char *>(ctx->small);
-    char *hsm = static_cast<char *>(ctx->small_host);
+    char *dsm = ctx->small.as<char>();
+    char *hsm = ctx->small_host.as<char>();
     // 2. regular samples + local size
     hipLaunchKernelGGL((sample_kernel<T>), dim3((S + 255) / 256), dim3(256), 0, s, d_keys,
                        (uint64_t)n_local, S, reinterpret_cast<T *>(dsm + off_samp));
@@ -621,9 +613,9 @@ static int sample_sort(dsort_ctx *ctx, const T *d_in, size_t n_local, T **d_out,
     } else {
         // [S samples | n_local] per rank through the caller's all-gather
         const size_t rec = (size_t)S * sizeof(T) + 8;
-        rc = ensure_host(ctx, &ctx->xfer, &ctx->xfer_bytes, rec * (size_t)(P + 1));
+        rc = ensure_host(ctx, ctx->xfer, rec * (size_t)(P + 1));
         if (rc) return rc;
-        char *mine = static_cast<char *>(ctx->xfer), *all = mine + rec;
+        char *mine = ctx->xfer.as<char>(), *all = mine + rec;
         DSORT_HIP(ctx, hipMemcpyAsync(mine, dsm + off_samp, (size_t)S * sizeof(T), hipMemcpyDeviceToHost, s));
         rc = exch_wait(ctx, s, true, deadline, "local sort");
         if (rc) return rc;
@@ -673,31 +665,33 @@ static int sample_sort(dsort_ctx *ctx, const T *d_in, size_t n_local, T **d_out,
         roff[r + 1] = roff[r] + rlen[r];
     }
     const uint64_t nrecv = roff[P];
-    rc = ensure(ctx, &ctx->recv, &ctx->recv_bytes, (nrecv ? nrecv : 1) * sizeof(T), "receive buffer");
+    rc = ensure(ctx, ctx->recv, (nrecv ? nrecv : 1) * sizeof(T), "receive buffer");
     if (rc) return rc;
-    rc = ensure(ctx, &ctx->recv2, &ctx->recv2_bytes, (nrecv ? nrecv : 1) * sizeof(T), "merge output");
+    rc = ensure(ctx, ctx->recv2, (nrecv ? nrecv : 1) * sizeof(T), "merge output");
     if (rc) return rc;
-    T *rb = static_cast<T *>(ctx->recv);
+    T *rb = ctx->recv.as<T>();
     exchange_fault_point(ctx, 2);
     uint64_t sent = 0;
     for (int r = 0; r < P; ++r) sent += r == me ? 0 : hcnt[r];
-    if ((rc = stage_event(ctx, 5, s))) return rc;
+    if ((rc = stage_event(ctx, s, true, kEvAllToAll0))) return rc;
     // 7. key exchange: one send and one receive per peer link, grouped (RCCL all-to-all-v), or
     //    host-staged: D2H the sorted run, exchange, H2D the received runs.  Stage event 6 sits behind
     //    the peers' keys: in front of RCCL's own part.
     const A2av a{d_keys, hcnt.data(), hcut.data(), n_local, rb, rlen.data(), roff.data(), nrecv, sizeof(T), nccl_type<T>()};
     if ((rc = a2av_peers(ctx, a, s, deadline, "key all-to-all", "key staging"))) return rc;
-    if ((rc = stage_event(ctx, 6, s)) || (rc = a2av_own(ctx, a, s)) || (rc = stage_event(ctx, 3, s))) return rc;
+    if ((rc = stage_event(ctx, s, true, kEvAllToAll1)) || (rc = a2av_own(ctx, a, s)) ||
+        (rc = stage_event(ctx, s, true, kEvExchangeDone)))
+        return rc;
     // 8. merge the P received runs (source-rank order keeps the merge deterministic); the
     // local sort's statistics and per-launch events stay
-    T *outp = static_cast<T *>(ctx->recv2);
+    T *outp = ctx->recv2.as<T>();
     rc = merge_device<T>(ctx, rb, rlen.data(), P, outp, s, true);
     if (rc) return rc;
     if (!host_tx) {  // the receives must have landed before the caller reads the slice
         rc = exch_wait(ctx, s, true, deadline, "key all-to-all", ctx->opt.test_hold_exchange != 0);
         if (rc) return rc;
     }
-    if ((rc = stage_event(ctx, 4, s))) return rc;
+    if ((rc = stage_event(ctx, s, true, kEvFinalDone))) return rc;
     ctx->last_stream = s;
     st.keys_out = nrecv;
     st.keys_sent = sent;

@@ -293,12 +293,6 @@ static void launch_place(hipStream_t s, unsigned G, const uint32_t *idx, uint64_
                        req, reply, dst);
 }
 
-static bool leg_event(dsort_ctx *ctx, int i, hipStream_t s) {
-    if (!ctx->ev_ok || !ctx->opt.stage_timing) return false;
-    if (!ctx->gat_ev[i] && hipEventCreate(&ctx->gat_ev[i]) != hipSuccess) return false;
-    return hipEventRecord(ctx->gat_ev[i], s) == hipSuccess;
-}
-
 static int plan_table(int nranks, const uint64_t *first, const uint64_t *count, uint64_t *lo, uint64_t *hi,
                       int32_t *owner, int *nranges) {
     std::vector<int> order;
@@ -334,7 +328,7 @@ static int sample_gather(dsort_ctx *ctx, const uint32_t *src, size_t n_src, uint
         call.finished();  // (every rank leaves here)
         return set_err(ctx, DSORT_EINVAL, "gather: more than 256 ranks (the owner table's fixed size)");
     }
-    ctx->gat_ev_ok = false;
+    ctx->gat_clk.start(ctx->ev_ok && ctx->opt.stage_timing);  // (the legs' events, for dsort_sample_gather_leg_ms)
     int rc = order_begin(ctx, s);
     if (rc) return rc;
 
@@ -367,15 +361,15 @@ static int sample_gather(dsort_ctx *ctx, const uint32_t *src, size_t n_src, uint
     const size_t off_bs = off_cnt + (((size_t)(G ? G : 1) * NB * 4 + 7) & ~(size_t)7);  // NB uint32
     const size_t off_tot = off_bs + (((size_t)NB * 4 + 7) & ~(size_t)7);            // NB uint64
     const size_t small_total = off_tot + (size_t)NB * 8;
-    rc = ensure(ctx, &ctx->gat_small, &ctx->gat_small_bytes, small_total, "gather routing tables");
+    rc = ensure(ctx, ctx->gat_small, small_total, "gather routing tables");
     if (rc) return rc;
-    rc = ensure_host(ctx, &ctx->gat_host, &ctx->gat_host_bytes, off_cnt + (size_t)(MAXR + 1) * 8);
+    rc = ensure_host(ctx, ctx->gat_host, off_cnt + (size_t)(MAXR + 1) * 8);
     if (rc) return rc;
-    rc = ensure(ctx, &ctx->gat_req, &ctx->gat_req_bytes, (n_idx ? n_idx : 1) * 4, "gather requests");
+    rc = ensure(ctx, ctx->gat_req, (n_idx ? n_idx : 1) * 4, "gather requests");
     if (rc) return rc;
-    char *dsm = static_cast<char *>(ctx->gat_small);
-    uint32_t *htab = static_cast<uint32_t *>(ctx->gat_host);
-    uint64_t *htot = reinterpret_cast<uint64_t *>(static_cast<char *>(ctx->gat_host) + off_cnt);
+    char *dsm = ctx->gat_small.as<char>();
+    uint32_t *htab = ctx->gat_host.as<uint32_t>();
+    uint64_t *htot = reinterpret_cast<uint64_t *>(ctx->gat_host.as<char>() + off_cnt);
     for (int i = 0; i < MAXR; ++i) {
         htab[i] = i < nr ? (uint32_t)lo[i] : 0u;
         htab[MAXR + i] = i < nr ? (uint32_t)(hi[i] - 1) : 0u;
@@ -385,11 +379,11 @@ static int sample_gather(dsort_ctx *ctx, const uint32_t *src, size_t n_src, uint
     uint32_t *wgcnt = reinterpret_cast<uint32_t *>(dsm + off_cnt);
     uint32_t *binstart = reinterpret_cast<uint32_t *>(dsm + off_bs);
     uint64_t *dtot = reinterpret_cast<uint64_t *>(dsm + off_tot);
-    uint32_t *req = static_cast<uint32_t *>(ctx->gat_req);
+    uint32_t *req = ctx->gat_req.as<uint32_t>();
     DSORT_HIP(ctx, hipMemcpyAsync(dsm, htab, off_cnt, hipMemcpyHostToDevice, s));
 
     // 1. route: count, scan, starts, place
-    bool ev = leg_event(ctx, 0, s);
+    ctx->gat_clk.mark(s);
     if (G) {
         launch_place<COUNT, 4>(s, G, idx, n_idx, chunk, tab, nr, P, wgcnt, binstart, nullptr, nullptr, nullptr);
         DSORT_HIP(ctx, hipGetLastError());
@@ -402,7 +396,7 @@ static int sample_gather(dsort_ctx *ctx, const uint32_t *src, size_t n_src, uint
         launch_place<ROUTE, 4>(s, G, idx, n_idx, chunk, tab, nr, P, wgcnt, binstart, req, nullptr, nullptr);
         DSORT_HIP(ctx, hipGetLastError());
     }
-    ev = leg_event(ctx, 1, s) && ev;
+    ctx->gat_clk.mark(s);
     DSORT_HIP(ctx, hipMemcpyAsync(htot, dtot, (size_t)NB * 8, hipMemcpyDeviceToHost, s));
     rc = exch_wait(ctx, s, true, deadline, "gather routing");
     if (rc) return rc;
@@ -430,49 +424,48 @@ static int sample_gather(dsort_ctx *ctx, const uint32_t *src, size_t n_src, uint
         if (r != me) sent += scnt[r];
     }
     if (so != (uint64_t)n_idx) return set_err(ctx, DSORT_EHIP, "gather: the routing counts do not add up");
-    rc = ensure(ctx, &ctx->gat_rreq, &ctx->gat_rreq_bytes, (m ? m : 1) * 4, "gather requests received");
+    rc = ensure(ctx, ctx->gat_rreq, (m ? m : 1) * 4, "gather requests received");
     if (rc) return rc;
-    rc = ensure(ctx, &ctx->gat_rep, &ctx->gat_rep_bytes, (m ? m : 1) * (size_t)W, "gather replies");
+    rc = ensure(ctx, ctx->gat_rep, (m ? m : 1) * (size_t)W, "gather replies");
     if (rc) return rc;
-    rc = ensure(ctx, &ctx->gat_back, &ctx->gat_back_bytes, (n_idx ? n_idx : 1) * (size_t)W, "gather records received");
+    rc = ensure(ctx, ctx->gat_back, (n_idx ? n_idx : 1) * (size_t)W, "gather records received");
     if (rc) return rc;
-    uint32_t *rreq = static_cast<uint32_t *>(ctx->gat_rreq);
-    uint32_t *rep = static_cast<uint32_t *>(ctx->gat_rep);
-    uint32_t *back = static_cast<uint32_t *>(ctx->gat_back);
+    uint32_t *rreq = ctx->gat_rreq.as<uint32_t>();
+    uint32_t *rep = ctx->gat_rep.as<uint32_t>();
+    uint32_t *back = ctx->gat_back.as<uint32_t>();
 
     // 2. the requests
     // (requests and records travel as dwords)
     rc = alltoallv(ctx, A2av{req, scnt.data(), soff.data(), n_idx, rreq, rcnt.data(), roff.data(), m, 4, ncclUint32}, s,
                    deadline, "gather request all-to-all", "gather request all-to-all (staging)");
     if (rc) return rc;
-    ev = leg_event(ctx, 2, s) && ev;
+    ctx->gat_clk.mark(s);
 
     // 3. serve them from this rank's records (m > 0: it owns some, so src is not NULL)
     if (m) {
         rc = dsort_gather_dev(ctx, src, rreq, rep, (size_t)m, W, stream);
         if (rc) return rc;
     }
-    ev = leg_event(ctx, 3, s) && ev;
+    ctx->gat_clk.mark(s);
 
     // the replies: the reverse exchange
     rc = alltoallv(ctx, A2av{rep, rcnt.data(), roff.data(), m, back, scnt.data(), soff.data(), n_idx, W, ncclUint32}, s,
                    deadline, "gather reply all-to-all", "gather reply all-to-all (staging)");
     if (rc) return rc;
     call.finished();
-    ev = leg_event(ctx, 4, s) && ev;
+    ctx->gat_clk.mark(s);
 
     // 4. unroute: dst[j] = back[pos(j)]
     if (G) {
         launch_place<UNROUTE, W>(s, G, idx, n_idx, chunk, tab, nr, P, wgcnt, binstart, nullptr, back, dst);
         DSORT_HIP(ctx, hipGetLastError());
     }
-    ev = leg_event(ctx, 5, s) && ev;
+    ctx->gat_clk.mark(s);
     if (!call.host_tx) {  // the receives must have landed before the caller reads dst
         rc = exch_wait(ctx, s, true, deadline, "gather reply all-to-all");
         if (rc) return rc;
     }
     if ((rc = order_end(ctx, s))) return rc;
-    ctx->gat_ev_ok = ev;
     ctx->stats.gather_sent = (size_t)sent;
     ctx->stats.gather_served = (size_t)m;
     return DSORT_OK;
@@ -542,14 +535,11 @@ int dsort_plan_gather_route(int nranges, const uint64_t lo[], const uint64_t hi[
 // until that call has finished; DSORT_EINVAL when it recorded none.
 int dsort_sample_gather_leg_ms(dsort_ctx *ctx, double ms[5]) {
     if (!ctx || !ms) return DSORT_EINVAL;
-    if (!ctx->gat_ev_ok) return set_err(ctx, DSORT_EINVAL, "no timed gather on this context");
-    DSORT_HIP(ctx, hipEventSynchronize(ctx->gat_ev[5]));
-    for (int i = 0; i < 5; ++i) {
-        float f = 0;
-        DSORT_HIP(ctx, hipEventElapsedTime(&f, ctx->gat_ev[i], ctx->gat_ev[i + 1]));
-        ms[i] = f;
-    }
-    return DSORT_OK;
+    const LegClock &c = ctx->gat_clk;
+    if (!c.complete(6)) return set_err(ctx, DSORT_EINVAL, "no timed gather on this context");
+    int rc = c.wait_last(ctx);
+    for (int i = 0; i < 5 && !rc; ++i) rc = c.elapsed(ctx, i, i + 1, &ms[i]);
+    return rc;
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include <atomic>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "dsort.h"
@@ -48,6 +49,92 @@ struct PassDesc {
     const uint32_t *tile_group = nullptr;  // irregular, optional: group of every output tile
 };
 
+// ----------------------------------------------------------------------------------------
+// What the context owns.  Each member frees or destroys itself when the context is deleted, so
+// dsort_finalize keeps no list of them.
+// ----------------------------------------------------------------------------------------
+// A grow-only arena and its size: device memory (DevBuf) or pinned host memory (HostBuf).  ensure()
+// and ensure_host() below grow them; a buffer they replace goes through release_dev / release_host.
+template <hipError_t (*Free)(void *)>
+struct Buf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    Buf() = default;
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    ~Buf() {
+        if (p) (void)Free(p);
+    }
+    template <class T>
+    T *as() const {
+        return static_cast<T *>(p);
+    }
+    void swap(Buf &o) {
+        std::swap(p, o.p);
+        std::swap(bytes, o.bytes);
+    }
+};
+using DevBuf = Buf<hipFree>;
+using HostBuf = Buf<hipHostFree>;
+
+// An event or a stream the context created (`h` is null until then); reads as the plain handle.
+template <class H, hipError_t (*Destroy)(H)>
+struct Owned {
+    H h = nullptr;
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    ~Owned() {
+        if (h) (void)Destroy(h);
+    }
+    operator H() const { return h; }
+};
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+
+// Stage events of a sort (dsort_ctx::ev; dsort_get_stats reads the times between them).
+enum StageEv {
+    kEvStart = 0,
+    kEvTileSortDone = 1,
+    kEvLocalDone = 2,     // the local sort done
+    kEvExchangeDone = 3,
+    kEvFinalDone = 4,     // the final merge (the bucket exchange: the last wave) done
+    kEvAllToAll0 = 5, kEvAllToAll1 = 6,  // around the key all-to-all
+    kEvTile0 = 7, kEvTile1 = 8,          // around the tile sort kernel
+    kEvHist0 = 9, kEvHist1 = 10,         // around the first-level histogram
+    kEvScatter0 = 11, kEvScatter1 = 12,  // around the first-level scatter
+    kEvSub0 = 13, kEvSub1 = 14,          // around the second-level partition
+    kWave0Offset = 15,  // the bucket exchange's first wave records kEvTileSortDone, kEvTile0/1 and kEvSub0/1
+                        // this much higher (dsort_ctx::ev_off), and its end at kEvWave0Done
+    kEvWave0Done = 16,
+    kStageEvents = 30
+};
+
+// The leg timer of a feature: HIP events around the legs of its last call, created on first use,
+// for its dsort_*_leg_ms reader.  start() opens a recording, mark() appends the next event; an
+// event that fails ends the recording, and count() is then 0, as it is when nothing was recorded.
+struct LegClock {
+    static constexpr int kMax = 14;  // (the top-k select: two per histogram pass of six, and 12 / 13)
+    Event ev[kMax];
+    int n = 0;        // events of the recording so far (mark_at: one past the highest index)
+    bool ok = false;  // recording, and every event so far went in
+    void start(bool enabled) {
+        n = 0;
+        ok = enabled;
+    }
+    void mark(hipStream_t s) { mark_at(n, s); }
+    void mark_at(int i, hipStream_t s) {
+        if (!ok || i >= kMax) return;
+        ok = (ev[i].h || hipEventCreate(&ev[i].h) == hipSuccess) && hipEventRecord(ev[i], s) == hipSuccess;
+        if (ok) n = i + 1;
+    }
+    int count() const { return ok ? n : 0; }
+    bool complete(int events) const { return count() == events; }
+    // for the readers: blocks until the last event, then ms between events a and b
+    int wait_last(dsort_ctx *ctx) const;
+    int elapsed(dsort_ctx *ctx, int a, int b, double *ms) const;
+};
+
 }  // namespace dsort
 
 // Per-context options (dsort_set_option; defaults = the tuned values).
@@ -75,6 +162,12 @@ struct dsort_opts {
 
 // The context.  One per host thread, bound to one device.
 struct dsort_ctx {
+    using DevBuf = dsort::DevBuf;
+    using HostBuf = dsort::HostBuf;
+    using Event = dsort::Event;
+    using Stream = dsort::Stream;
+    using LegClock = dsort::LegClock;
+
     dsort_opts opt;
     int nested = 0;  // > 0 inside a sort the library runs for itself (the splitter-sample sort):
                      // such a sort never buckets and never fires the fault injection
@@ -82,163 +175,116 @@ struct dsort_ctx {
     std::atomic<int> abort_req{0};  // dsort_comm_abort from another thread during an exchange
     std::mutex comm_mu;             // held by a running exchange / communicator set-up (dsort.h)
     int device = 0;
-    hipStream_t stream = nullptr;
     std::string err;
+
+    // Members are destroyed last to first (dsort_finalize: delete ctx, on the context's device): the
+    // buffers below go first, then the events, then the streams.
+    Stream stream;
+    Stream side;   // copies that overlap the first-level scatter (both directions)
+    Stream xs;     // bucket exchange: the comm stream of its sends and receives
+
+    Event groups_ev;   // last H2D copy out of groups_host
+    Event bucket_ev;
+    Event sub_ev;
+    Event side_ev;     // side -> sort stream
+    Event ready_ev;    // sort stream -> side
+    // End of the last sort / merge on its stream: a call on another stream waits for it, since
+    // the arenas are shared and a call returns while its last kernels still run.
+    Event done_ev;
+    Event a64_mm_ev;   // the int64 argsort's min/max read-back into small_host
+    Event xev[3];      // bucket exchange: a wave's receives done (0, 1), the partition done (2)
+    Event ev[dsort::kStageEvents];  // stage timing (StageEv)
+    static constexpr int kMaxKev = 128;  // per-launch events of the merge kernel (2 per pass)
+    Event kev[kMaxKev];
+    // the legs' events of the last call of a feature (its dsort_*_leg_ms reader)
+    LegClock pairs_clk;  // the pair sort (dsort_pairs.hip): pack, sort and unpack
+    LegClock a64_clk;    // the int64 argsort (dsort_pairs64.hip)
+    LegClock s64_clk;    // the int64 argsort across ranks
+    LegClock tk_clk;     // the top-k select's histogram kernels and compaction (on request)
+    LegClock gat_clk;    // the distributed gather's five legs
+
     // grow-only device arenas
-    void *scratch = nullptr;
-    size_t scratch_bytes = 0;
-    void *splits = nullptr;   // per-tile split vectors of a k-way pass (uint32 x F per tile)
-    size_t splits_bytes = 0;
-    void *groups = nullptr;   // irregular group tables (device)
-    size_t groups_bytes = 0;
-    void *groups_host = nullptr;  // pinned staging of the group tables
-    size_t groups_host_bytes = 0;
-    hipEvent_t groups_ev = nullptr;  // last H2D copy out of groups_host
+    DevBuf scratch;
+    DevBuf splits;   // per-tile split vectors of a k-way pass (uint32 x F per tile)
+    DevBuf groups;   // irregular group tables (device)
+    HostBuf groups_host;  // pinned staging of the group tables
     bool groups_ev_pending = false;
-    void *scratch2 = nullptr; // second scratch for multi-level irregular merges
-    size_t scratch2_bytes = 0;
-    void *io = nullptr;        // staging for the host-buffer entry points
-    size_t io_bytes = 0;
-    void *io2 = nullptr;
-    size_t io2_bytes = 0;
-    void *pairs = nullptr;     // packed (key, value) words of the pair sort (dsort_pairs.hip): 8 B each
-    size_t pairs_bytes = 0;
-    hipEvent_t pairs_ev[4] = {};  // around its pack, sort and unpack legs (created on first use)
-    bool pairs_ev_ok = false;     // ... all four recorded by the last pair sort
-    void *spairs_k = nullptr;     // the pair sample sort's slice, unpacked: sorted keys (4 B each) ...
-    size_t spairs_k_bytes = 0;
-    void *spairs_v = nullptr;     // ... and their indices / values
-    size_t spairs_v_bytes = 0;
+    DevBuf scratch2; // second scratch for multi-level irregular merges
+    DevBuf io;        // staging for the host-buffer entry points
+    DevBuf io2;
+    DevBuf pairs;     // packed (key, value) words of the pair sort (dsort_pairs.hip): 8 B each
+    DevBuf spairs_k;     // the pair sample sort's slice, unpacked: sorted keys (4 B each) ...
+    DevBuf spairs_v;     // ... and their indices / values
     // the int64 argsort and record sort (dsort_pairs64.hip); its first arena is `pairs`
-    void *a64_b = nullptr;        // the wide path's second arena of packed words: 8 B each
-    size_t a64_b_bytes = 0;
-    void *a64_idx = nullptr;      // the record sort's permutation: 4 B each
-    size_t a64_idx_bytes = 0;
-    void *a64_part = nullptr;     // the min/max reduction's per-workgroup partials and its result
-    size_t a64_part_bytes = 0;
-    hipEvent_t a64_mm_ev = nullptr;  // the min/max read-back into small_host
-    static constexpr int kA64Ev = 7;
-    hipEvent_t a64_ev[kA64Ev] = {};  // around its legs (created on first use)
-    int a64_legs = 0;             // ... those the last call recorded
-    bool a64_ev_ok = false;       // ... all of them
+    DevBuf a64_b;        // the wide path's second arena of packed words: 8 B each
+    DevBuf a64_idx;      // the record sort's permutation: 4 B each
+    DevBuf a64_part;     // the min/max reduction's per-workgroup partials and its result
     bool a64_minmax = false;      // the last call ran the reduction (the automatic mode)
     // the int64 argsort across ranks (dsort_sample_argsort_dev_i64, dsort_pairs64.hip); its packed
     // words start in `pairs`
-    void *s64_k = nullptr;        // this rank's slice: sorted keys (8 B each) ...
-    size_t s64_k_bytes = 0;
-    void *s64_i = nullptr;        // ... and their global positions (4 B each)
-    size_t s64_i_bytes = 0;
-    void *s64_sa = nullptr;       // wide: the first sort's slice, saved (the second sort reuses recv2)
-    size_t s64_sa_bytes = 0;
-    void *s64_pos = nullptr;      // wide: the low words of a slice, the indices of a gather (4 B each)
-    size_t s64_pos_bytes = 0;
-    void *s64_got = nullptr;      // wide: what a gather brought (8 B per index)
-    size_t s64_got_bytes = 0;
-    static constexpr int kS64Ev = 11;
-    hipEvent_t s64_ev[kS64Ev] = {};  // around its legs (created on first use)
-    int s64_legs = 0;             // ... those the last call recorded
-    bool s64_ev_ok = false;       // ... all of them
+    DevBuf s64_k;        // this rank's slice: sorted keys (8 B each) ...
+    DevBuf s64_i;        // ... and their global positions (4 B each)
+    DevBuf s64_sa;       // wide: the first sort's slice, saved (the second sort reuses recv2)
+    DevBuf s64_pos;      // wide: the low words of a slice, the indices of a gather (4 B each)
+    DevBuf s64_got;      // wide: what a gather brought (8 B per index)
     // the typed-key sample sort and sample argsort (dsort_keys.hip): this rank's chunk, encoded -- the
     // input of the integer call behind them
-    void *kenc = nullptr;
-    size_t kenc_bytes = 0;
+    DevBuf kenc;
     // top-k selection (dsort_topk.hip); the 4-byte candidates' packed words go to `pairs`, the order
     // of the 8-byte candidates to `a64_idx`
-    void *tk_rows = nullptr;      // one pass's histogram rows: 2048 bins per workgroup (4 B each)
-    size_t tk_rows_bytes = 0;
-    void *tk_small = nullptr;     // the state, the partial column sums, less / eq / quota / offsets
-    size_t tk_small_bytes = 0;
-    void *tk_ck = nullptr;        // the candidates: 8-byte keys, or the packed words a rank sends (8 B each);
-    size_t tk_ck_bytes = 0;       // the full path's sorted keys
-    void *tk_cp = nullptr;        // ... and the positions of 8-byte candidates (4 B each)
-    size_t tk_cp_bytes = 0;
-    void *tk_rk = nullptr;        // across ranks, 8-byte keys: every rank's candidates ...
-    size_t tk_rk_bytes = 0;
-    void *tk_rp = nullptr;        // ... their positions ...
-    size_t tk_rp_bytes = 0;
-    void *tk_sk = nullptr;        // ... and the candidates in key order
-    size_t tk_sk_bytes = 0;
-    hipEvent_t tk_ev[14] = {};    // around the select's histogram kernels and compaction (on request)
+    DevBuf tk_rows;      // one pass's histogram rows: 2048 bins per workgroup (4 B each)
+    DevBuf tk_small;     // the state, the partial column sums, less / eq / quota / offsets
+    DevBuf tk_ck;        // the candidates: 8-byte keys, or the packed words a rank sends (8 B each);
+                         // the full path's sorted keys
+    DevBuf tk_cp;        // ... and the positions of 8-byte candidates (4 B each)
+    DevBuf tk_rk;        // across ranks, 8-byte keys: every rank's candidates ...
+    DevBuf tk_rp;        // ... their positions ...
+    DevBuf tk_sk;        // ... and the candidates in key order
     bool tk_timing = false;       // dsort_topk_leg_timing
     int tk_passes = 0;            // histogram passes the last select timed (0: none)
     // the distributed gather (dsort_gather.hip): arenas of its own, so that a gather leaves the
     // slices of the preceding sample sort / argsort (recv2, spairs_k, spairs_v) alone
-    void *gat_req = nullptr;      // this rank's requests, owner-major (4 B per index)
-    size_t gat_req_bytes = 0;
-    void *gat_rreq = nullptr;     // the requests received (4 B each)
-    size_t gat_rreq_bytes = 0;
-    void *gat_rep = nullptr;      // the records served (W bytes per request received)
-    size_t gat_rep_bytes = 0;
-    void *gat_back = nullptr;     // the records that came back (W bytes per index)
-    size_t gat_back_bytes = 0;
-    void *gat_small = nullptr;    // owner table, per-workgroup counts, bin starts and totals
-    size_t gat_small_bytes = 0;
-    void *gat_host = nullptr;     // pinned: the owner table and the bin totals
-    size_t gat_host_bytes = 0;
-    hipEvent_t gat_ev[6] = {};    // around its five legs (created on first use)
-    bool gat_ev_ok = false;       // ... all six recorded by the last gather
-    void *bucket = nullptr;       // partition pass of the bucketed int32 sort (dsort_bucket.h)
-    size_t bucket_bytes = 0;
-    void *bucket_host = nullptr;  // pinned: bucket starts
-    size_t bucket_host_bytes = 0;
-    hipEvent_t bucket_ev = nullptr;
-    void *sub = nullptr;          // second partition level (dsort_sub.h)
-    size_t sub_bytes = 0;
-    void *sub_alt = nullptr;      // the bucket exchange's second wave uses the other of the two
-    size_t sub_alt_bytes = 0;     // (the first wave's kernels still read theirs)
-    void *stmp = nullptr;         // merge output of a split sub-bucket (merge_split_subbuckets)
-    size_t stmp_bytes = 0;
-    void *sub_host = nullptr;     // pinned: bucket table, chunk table, tile / merge-record counts
-    size_t sub_host_bytes = 0;
-    hipEvent_t sub_ev = nullptr;
-    hipStream_t side = nullptr;   // copies that overlap the first-level scatter (both directions)
-    hipEvent_t side_ev = nullptr;  // side -> sort stream
-    hipEvent_t ready_ev = nullptr; // sort stream -> side
-    // End of the last sort / merge on its stream: a call on another stream waits for it, since
-    // the arenas are shared and a call returns while its last kernels still run.
-    hipEvent_t done_ev = nullptr;
-    hipStream_t done_stream = nullptr;
+    DevBuf gat_req;      // this rank's requests, owner-major (4 B per index)
+    DevBuf gat_rreq;     // the requests received (4 B each)
+    DevBuf gat_rep;      // the records served (W bytes per request received)
+    DevBuf gat_back;     // the records that came back (W bytes per index)
+    DevBuf gat_small;    // owner table, per-workgroup counts, bin starts and totals
+    HostBuf gat_host;    // pinned: the owner table and the bin totals
+    DevBuf bucket;       // partition pass of the bucketed int32 sort (dsort_bucket.h)
+    HostBuf bucket_host; // pinned: bucket starts
+    DevBuf sub;          // second partition level (dsort_sub.h)
+    DevBuf sub_alt;      // the bucket exchange's second wave uses the other of the two
+                         // (the first wave's kernels still read theirs)
+    DevBuf stmp;         // merge output of a split sub-bucket (merge_split_subbuckets)
+    HostBuf sub_host;    // pinned: bucket table, chunk table, tile / merge-record counts
+    hipStream_t done_stream = nullptr;  // (done_ev)
     bool done_pending = false;
-    void *tfb = nullptr;          // tiles the bin sort declined (+ their count, on the device)
-    size_t tfb_bytes = 0;
-    void *text_status = nullptr;  // per-tile counts and their prefixes of the text codec
-    size_t text_status_bytes = 0;
-    void *red = nullptr;       // 64 B of reduction accumulators
-    uint64_t *red_host = nullptr;  // pinned mirror
+    DevBuf tfb;          // tiles the bin sort declined (+ their count, on the device)
+    DevBuf text_status;  // per-tile counts and their prefixes of the text codec
+    DevBuf red;       // 64 B of reduction accumulators
+    HostBuf red_host; // pinned mirror
     // sample sort (multi-GPU)
     ncclComm *comm = nullptr;
     bool has_transport = false;   // host transport instead of RCCL (dsort_comm_init_transport)
     dsort_transport transport = {};
     dsort::TxSeq *tx = nullptr;   // the running sample sort's host-transport sequence (dsort_tx.h)
-    void *xfer = nullptr;         // pinned host staging of the host transport
-    size_t xfer_bytes = 0;
-    void *xfer2 = nullptr;
-    size_t xfer2_bytes = 0;
-    void *fence = nullptr;        // DSORT_OPT_TEST_WAVE_FENCE: fingerprints (device, pinned mirror)
-    size_t fence_bytes = 0;
-    void *fence_host = nullptr;
-    size_t fence_host_bytes = 0;
+    HostBuf xfer;         // pinned host staging of the host transport
+    HostBuf xfer2;
+    DevBuf fence;        // DSORT_OPT_TEST_WAVE_FENCE: fingerprints (device, pinned mirror)
+    HostBuf fence_host;
     int nranks = 1;
     int rank = 0;
-    void *local = nullptr;  // locally sorted chunk
-    size_t local_bytes = 0;
-    void *recv = nullptr;
-    size_t recv_bytes = 0;
-    void *recv2 = nullptr;
-    size_t recv2_bytes = 0;
-    void *small = nullptr;  // samples / splitters / counts on device
-    size_t small_bytes = 0;
-    void *small_host = nullptr;  // pinned
-    size_t small_host_bytes = 0;
-    void *bxs = nullptr;    // bucket exchange: this rank's and every rank's splitter samples
-    size_t bxs_bytes = 0;
+    DevBuf local;  // locally sorted chunk
+    DevBuf recv;
+    DevBuf recv2;
+    DevBuf small;  // samples / splitters / counts on device
+    HostBuf small_host;  // pinned
+    DevBuf bxs;    // bucket exchange: this rank's and every rank's splitter samples
     const uint32_t *bk_hot = nullptr;  // the last first level's runs flag (device, BkMap.hot)
-    hipStream_t xs = nullptr;     // bucket exchange: the comm stream of its sends and receives
-    hipEvent_t xev[3] = {};       // ... a wave's receives done (0, 1), the partition done (2)
-    int ev_off = 0;               // stage events 1, 7, 8, 13, 14 of the bucket exchange's first
-                                  // wave go to 16, 22, 23, 28, 29 (dsort_get_stats adds them up)
-    int ev_done = 2;        // the stage event a sort's second level records at its end (the bucket
-                            // exchange records its own end as event 4)
+    int ev_off = 0;               // kWave0Offset while the bucket exchange's first wave runs its second
+                                  // level and tile sort (dsort_get_stats adds the two waves up)
+    int ev_done = dsort::kEvLocalDone;  // the stage event a sort's second level records at its end (the
+                                        // bucket exchange: kEvWave0Done, then kEvFinalDone)
     // The bucket exchange runs its second level while the keys are still in flight: the sort's
     // host waits then poll (abort flag, deadline) instead of blocking on a stream a dead peer
     // would never complete (sync_event / sync_stream, dsort_wave.hip).
@@ -251,15 +297,8 @@ struct dsort_ctx {
     std::vector<void *> dev_later, host_later;
     uint64_t deferred_n = 0;  // arenas whose release was deferred so far (stats.deferred_frees)
     // stage timing
-    hipEvent_t ev[30] = {};  // 0 start, 1 tile sort done, 2 local sort done, 3 exchange done,
-                             // 4 final merge done, 5/6 around the key all-to-all, 7/8 around the
-                             // tile sort kernel, 9/10 around the first-level histogram, 11/12
-                             // around the first-level scatter, 13/14 around the second-level
-                             // partition
     unsigned ev_mask = 0;             // events recorded by the last call (bit i = ev[i])
     hipStream_t last_stream = nullptr;  // stream of the last asynchronous call
-    static constexpr int kMaxKev = 128;  // per-launch events of the merge kernel (2 per pass)
-    hipEvent_t kev[kMaxKev] = {};
     int kev_used = 0;
     bool ev_ok = false;       // stage events recorded: created, and DSORT_OPT_STAGE_TIMING on
     bool ev_created = false;
@@ -290,14 +329,21 @@ int set_err(dsort_ctx *ctx, int code, const std::string &msg);
 // the stream argument of the C-ABI: NULL = the context's stream, DSORT_NULL_STREAM = stream 0
 hipStream_t pick_stream(dsort_ctx *ctx, void *stream);
 int hip_err(dsort_ctx *ctx, hipError_t e, const char *what);
-int ensure(dsort_ctx *ctx, void **buf, size_t *have, size_t need, const char *what);
-// grow-only pinned host buffers: any, and the mirror of ctx->small
-int ensure_host(dsort_ctx *ctx, void **buf, size_t *have, size_t need);
-int ensure_small_host(dsort_ctx *ctx, size_t need);
-// hipFree / hipHostFree of a replaced buffer, deferred while ctx->poll_waits (see dsort_ctx)
-void release_dev(dsort_ctx *ctx, void *p);
-void release_host(dsort_ctx *ctx, void *p);
+// grow-only: at least `need` bytes in the arena (the old contents are not kept)
+int ensure(dsort_ctx *ctx, DevBuf &buf, size_t need, const char *what);
+int ensure_host(dsort_ctx *ctx, HostBuf &buf, size_t need);
+// the pinned mirror of ctx->small (sized before any keys are in flight: it never grows while
+// ctx->poll_waits)
+inline int ensure_small_host(dsort_ctx *ctx, size_t need) { return ensure_host(ctx, ctx->small_host, need); }
+// hipFree / hipHostFree of a buffer that is being replaced, deferred while ctx->poll_waits (see
+// dsort_ctx); the buffer is empty afterwards
+void release_dev(dsort_ctx *ctx, DevBuf &buf);
+void release_host(dsort_ctx *ctx, HostBuf &buf);
 void flush_later(dsort_ctx *ctx);
+// Stage event e of a timed call on s, when stage timing is on (ctx->ev_ok); `timed` also opens and
+// closes the profiler ranges around the sort's kernels.  Records exactly ev[e]: the callers inside
+// the bucket exchange's waves add ctx->ev_off themselves.
+int stage_event(dsort_ctx *ctx, hipStream_t s, bool timed, StageEv e);
 
 // The sort and the k-way merge (dsort_wave.hip), both key widths.  All asynchronous on `s`.
 // sort_device sorts d_in[0..n) into d_keys (d_in may equal d_keys).  merge_device with

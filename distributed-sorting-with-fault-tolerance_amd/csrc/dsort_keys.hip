@@ -183,9 +183,9 @@ static int argsort_any(dsort_ctx *ctx, const void *keys, void *keys_out, uint32_
 // the input of the sample sort that follows, which may still read it for the context's previous
 // call on another stream: the caller has opened an order bracket.
 static int encode_chunk(dsort_ctx *ctx, const void *d_keys, size_t n, KeySpec k, hipStream_t s) {
-    int rc = ensure(ctx, &ctx->kenc, &ctx->kenc_bytes, (n ? n : 1) * (size_t)k.bytes, "typed-key sample sort words");
+    int rc = ensure(ctx, ctx->kenc, (n ? n : 1) * (size_t)k.bytes, "typed-key sample sort words");
     if (rc) return rc;
-    return n ? code_dev(ctx, d_keys, ctx->kenc, n, k, false, s) : DSORT_OK;
+    return n ? code_dev(ctx, d_keys, ctx->kenc.p, n, k, false, s) : DSORT_OK;
 }
 
 }  // namespace ky
@@ -257,12 +257,12 @@ int dsort_sort_keys(dsort_ctx *ctx, void *host_keys, size_t n, int key_type, int
     if (n < 2) return DSORT_OK;
     if (n > SIZE_MAX / 8) return set_err(ctx, DSORT_EINVAL, "sort: n * 8 bytes overflow size_t");
     const size_t bytes = n * (size_t)k.bytes;
-    int rc = ensure(ctx, &ctx->io, &ctx->io_bytes, bytes, "staging");
+    int rc = ensure(ctx, ctx->io, bytes, "staging");
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    DSORT_HIP(ctx, hipMemcpyAsync(ctx->io, host_keys, bytes, hipMemcpyHostToDevice, s));
-    if ((rc = dsort_sort_dev_keys(ctx, ctx->io, n, key_type, flags, nullptr))) return rc;
-    DSORT_HIP(ctx, hipMemcpyAsync(host_keys, ctx->io, bytes, hipMemcpyDeviceToHost, s));
+    DSORT_HIP(ctx, hipMemcpyAsync(ctx->io.p, host_keys, bytes, hipMemcpyHostToDevice, s));
+    if ((rc = dsort_sort_dev_keys(ctx, ctx->io.p, n, key_type, flags, nullptr))) return rc;
+    DSORT_HIP(ctx, hipMemcpyAsync(host_keys, ctx->io.p, bytes, hipMemcpyDeviceToHost, s));
     DSORT_HIP(ctx, hipStreamSynchronize(s));
     return DSORT_OK;
 }
@@ -284,16 +284,16 @@ int dsort_argsort_keys(dsort_ctx *ctx, const void *keys, void *keys_out, uint32_
     if (int rc = ky::check_argsort(ctx, keys, idx, n)) return rc;
     if (n == 0) return DSORT_OK;
     const size_t bytes = n * (size_t)k.bytes;
-    int rc = ensure(ctx, &ctx->io, &ctx->io_bytes, bytes, "staging");
+    int rc = ensure(ctx, ctx->io, bytes, "staging");
     if (rc) return rc;
-    rc = ensure(ctx, &ctx->io2, &ctx->io2_bytes, n * 4, "staging 2");
+    rc = ensure(ctx, ctx->io2, n * 4, "staging 2");
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    uint32_t *di = static_cast<uint32_t *>(ctx->io2);
-    DSORT_HIP(ctx, hipMemcpyAsync(ctx->io, keys, bytes, hipMemcpyHostToDevice, s));
-    const int src = ky::argsort_any(ctx, ctx->io, keys_out ? ctx->io : nullptr, di, n, k, s);
+    uint32_t *di = ctx->io2.as<uint32_t>();
+    DSORT_HIP(ctx, hipMemcpyAsync(ctx->io.p, keys, bytes, hipMemcpyHostToDevice, s));
+    const int src = ky::argsort_any(ctx, ctx->io.p, keys_out ? ctx->io.p : nullptr, di, n, k, s);
     if (src && src != DSORT_ESTAGE) return src;
-    if (keys_out) DSORT_HIP(ctx, hipMemcpyAsync(keys_out, ctx->io, bytes, hipMemcpyDeviceToHost, s));
+    if (keys_out) DSORT_HIP(ctx, hipMemcpyAsync(keys_out, ctx->io.p, bytes, hipMemcpyDeviceToHost, s));
     DSORT_HIP(ctx, hipMemcpyAsync(idx, di, n * 4, hipMemcpyDeviceToHost, s));
     DSORT_HIP(ctx, hipStreamSynchronize(s));
     return src;
@@ -326,9 +326,9 @@ int dsort_sort_records_dev_keys(dsort_ctx *ctx, const void *d_keys, void *d_keys
     // as dsort_sort_records_dev_i64: the argsort into an arena of the context, then the gather
     int rc = order_begin(ctx, s);
     if (rc) return rc;
-    rc = ensure(ctx, &ctx->a64_idx, &ctx->a64_idx_bytes, n * 4, "record sort indices");
+    rc = ensure(ctx, ctx->a64_idx, n * 4, "record sort indices");
     if (rc) return rc;
-    uint32_t *idx = static_cast<uint32_t *>(ctx->a64_idx);
+    uint32_t *idx = ctx->a64_idx.as<uint32_t>();
     const int src = ky::argsort_any(ctx, d_keys, d_keys_out, idx, n, k, s);
     if (src && src != DSORT_ESTAGE) return src;
     const std::string msg = ctx->err;
@@ -357,9 +357,9 @@ int dsort_sample_sort_dev_keys(dsort_ctx *ctx, const void *d_keys, size_t n_loca
     if (rc) return exch_leave(ctx, stream, rc);
     void *slice = nullptr;
     size_t m = 0;
-    rc = k.bytes == 4 ? dsort_sample_sort_dev_i32(ctx, static_cast<const int32_t *>(ctx->kenc), n_local,
+    rc = k.bytes == 4 ? dsort_sample_sort_dev_i32(ctx, ctx->kenc.as<const int32_t>(), n_local,
                                                   reinterpret_cast<int32_t **>(&slice), &m, stream)
-                      : dsort_sample_sort_dev_i64(ctx, static_cast<const int64_t *>(ctx->kenc), n_local,
+                      : dsort_sample_sort_dev_i64(ctx, ctx->kenc.as<const int64_t>(), n_local,
                                                   reinterpret_cast<int64_t **>(&slice), &m, stream);
     if (rc) return rc;
     // the slice is context-owned and ready after the stream, as it is for the integer call
@@ -394,10 +394,10 @@ int dsort_sample_argsort_dev_keys(dsort_ctx *ctx, const void *d_keys, size_t n_l
     size_t m = 0;
     // DSORT_ESTAGE of the 8-byte call: every leg has run and the outputs are valid
     const int src =
-        k.bytes == 4 ? dsort_sample_argsort_dev_i32(ctx, static_cast<const int32_t *>(ctx->kenc), n_local, first,
+        k.bytes == 4 ? dsort_sample_argsort_dev_i32(ctx, ctx->kenc.as<const int32_t>(), n_local, first,
                                                     d_keys_out ? reinterpret_cast<int32_t **>(&ko) : nullptr, &io, &m,
                                                     stream)
-                     : dsort_sample_argsort_dev_i64(ctx, static_cast<const int64_t *>(ctx->kenc), n_local, first,
+                     : dsort_sample_argsort_dev_i64(ctx, ctx->kenc.as<const int64_t>(), n_local, first,
                                                     d_keys_out ? reinterpret_cast<int64_t **>(&ko) : nullptr, &io, &m,
                                                     stream);
     if (src && !(src == DSORT_ESTAGE && k.bytes == 8)) return src;

@@ -206,13 +206,6 @@ static unsigned grid_for(uint64_t lanes) {
     return (unsigned)(g > MAXWG ? MAXWG : (g ? g : 1));
 }
 
-// The legs' events of the last pair sort (pack | sort | unpack), for dsort_pairs_leg_ms below.
-static bool leg_event(dsort_ctx *ctx, int i, hipStream_t s) {
-    if (!ctx->ev_ok || !ctx->opt.stage_timing) return false;
-    if (!ctx->pairs_ev[i] && hipEventCreate(&ctx->pairs_ev[i]) != hipSuccess) return false;
-    return hipEventRecord(ctx->pairs_ev[i], s) == hipSuccess;
-}
-
 // The launches of the typed kernels, defined at the end of the file: the int32 entry points'
 // kernels then come out of the compiler in the order, and so under the labels, they always had
 // (scripts/asm_digest.py compares them with the parent's).
@@ -254,26 +247,28 @@ int pairs_sort(dsort_ctx *ctx, const int32_t *keys_in, const uint32_t *vals_in, 
     // before and after the sort's own bracket: one bracket around all three legs.
     int rc = order_begin(ctx, s);
     if (rc) return rc;
-    rc = ensure(ctx, &ctx->pairs, &ctx->pairs_bytes, n * 8, "pair arena");
+    rc = ensure(ctx, ctx->pairs, n * 8, "pair arena");
     if (rc) return rc;
-    uint64_t *packed = static_cast<uint64_t *>(ctx->pairs);
-    ctx->pairs_ev_ok = leg_event(ctx, 0, s);
+    uint64_t *packed = ctx->pairs.as<uint64_t>();
+    // the legs' events (pack | sort | unpack), for dsort_pairs_leg_ms below
+    ctx->pairs_clk.start(ctx->ev_ok && ctx->opt.stage_timing);
+    ctx->pairs_clk.mark(s);
     const unsigned grid = grid_for((n + 3) / 4);
     rc = pack(ctx, keys_in, vals_in, packed, n, 0, s, kc);
     if (rc) return rc;
-    ctx->pairs_ev_ok = ctx->pairs_ev_ok && leg_event(ctx, 1, s);
+    ctx->pairs_clk.mark(s);
     // DSORT_OPT_KILL_AFTER_STAGE fires inside, as for any int64 sort of n keys; DSORT_ESTAGE (the
     // stage was never reached) leaves a valid output, so the unpack still runs
     const int src = sort_device<int64_t>(ctx, reinterpret_cast<int64_t *>(packed), reinterpret_cast<int64_t *>(packed),
                                          n, s, true);
     if (src && src != DSORT_ESTAGE) return src;
-    ctx->pairs_ev_ok = ctx->pairs_ev_ok && leg_event(ctx, 2, s);
+    ctx->pairs_clk.mark(s);
     if (kc)
         launch_unpack_keys(kc, grid, s, packed, keys_out, vals_out, (uint64_t)n);
     else
         hipLaunchKernelGGL(pairs_unpack_kernel, dim3(grid), dim3(NT), 0, s, packed, keys_out, vals_out, (uint64_t)n);
     DSORT_HIP(ctx, hipGetLastError());
-    ctx->pairs_ev_ok = ctx->pairs_ev_ok && leg_event(ctx, 3, s);
+    ctx->pairs_clk.mark(s);
     rc = order_end(ctx, s);
     return rc ? rc : src;
 }
@@ -299,12 +294,14 @@ static int sample_pairs_sort(dsort_ctx *ctx, const int32_t *keys_in, const uint3
     hipStream_t s = pick_stream(ctx, stream);
     int rc = order_begin(ctx, s);
     if (rc) return rc;
-    rc = ensure(ctx, &ctx->pairs, &ctx->pairs_bytes, (n ? n : 1) * 8, "pair arena");
+    rc = ensure(ctx, ctx->pairs, (n ? n : 1) * 8, "pair arena");
     if (rc) return rc;
-    uint64_t *packed = static_cast<uint64_t *>(ctx->pairs);
-    ctx->pairs_ev_ok = leg_event(ctx, 0, s);
+    uint64_t *packed = ctx->pairs.as<uint64_t>();
+    // the legs' events (pack | sort | unpack), for dsort_pairs_leg_ms below
+    ctx->pairs_clk.start(ctx->ev_ok && ctx->opt.stage_timing);
+    ctx->pairs_clk.mark(s);
     if (n && (rc = pack(ctx, keys_in, vals_in, packed, n, base, s))) return rc;
-    ctx->pairs_ev_ok = ctx->pairs_ev_ok && leg_event(ctx, 1, s);
+    ctx->pairs_clk.mark(s);
     int64_t *slice = nullptr;
     size_t m = 0;
     rc = sample_sort_packed(ctx, reinterpret_cast<const int64_t *>(packed), n, &slice, &m, stream);
@@ -312,20 +309,20 @@ static int sample_pairs_sort(dsort_ctx *ctx, const int32_t *keys_in, const uint3
     if (m && (reinterpret_cast<uintptr_t>(slice) & 15))
         return set_err(ctx, DSORT_EHIP, "pair sample sort: the sample sort's slice is not 16-byte aligned");
     if (keys_out) {
-        rc = ensure(ctx, &ctx->spairs_k, &ctx->spairs_k_bytes, (m ? m : 1) * 4, "pair sample sort keys");
+        rc = ensure(ctx, ctx->spairs_k, (m ? m : 1) * 4, "pair sample sort keys");
         if (rc) return rc;
     }
-    rc = ensure(ctx, &ctx->spairs_v, &ctx->spairs_v_bytes, (m ? m : 1) * 4, "pair sample sort values");
+    rc = ensure(ctx, ctx->spairs_v, (m ? m : 1) * 4, "pair sample sort values");
     if (rc) return rc;
-    int32_t *ko = keys_out ? static_cast<int32_t *>(ctx->spairs_k) : nullptr;
-    uint32_t *vo = static_cast<uint32_t *>(ctx->spairs_v);
-    ctx->pairs_ev_ok = ctx->pairs_ev_ok && leg_event(ctx, 2, s);
+    int32_t *ko = keys_out ? ctx->spairs_k.as<int32_t>() : nullptr;
+    uint32_t *vo = ctx->spairs_v.as<uint32_t>();
+    ctx->pairs_clk.mark(s);
     if (m) {
         hipLaunchKernelGGL(pairs_unpack_kernel, dim3(grid_for((m + 3) / 4)), dim3(NT), 0, s,
                            reinterpret_cast<const uint64_t *>(slice), ko, vo, (uint64_t)m);
         DSORT_HIP(ctx, hipGetLastError());
     }
-    ctx->pairs_ev_ok = ctx->pairs_ev_ok && leg_event(ctx, 3, s);
+    ctx->pairs_clk.mark(s);
     if ((rc = order_end(ctx, s))) return rc;
     if (keys_out) *keys_out = ko;
     *vals_out = vo;
@@ -400,13 +397,13 @@ int dsort_argsort_i32(dsort_ctx *ctx, const int32_t *keys, int32_t *keys_out, ui
         return set_err(ctx, DSORT_EINVAL, "argsort: more than 2^32 keys (a position must fit 32 bits)");
     if (n && (!keys || !idx)) return set_err(ctx, DSORT_EINVAL, "null argument");
     if (n == 0) return DSORT_OK;
-    int rc = ensure(ctx, &ctx->io, &ctx->io_bytes, n * 4, "staging");
+    int rc = ensure(ctx, ctx->io, n * 4, "staging");
     if (rc) return rc;
-    rc = ensure(ctx, &ctx->io2, &ctx->io2_bytes, n * 4, "staging 2");
+    rc = ensure(ctx, ctx->io2, n * 4, "staging 2");
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    int32_t *dk = static_cast<int32_t *>(ctx->io);
-    uint32_t *di = static_cast<uint32_t *>(ctx->io2);
+    int32_t *dk = ctx->io.as<int32_t>();
+    uint32_t *di = ctx->io2.as<uint32_t>();
     DSORT_HIP(ctx, hipMemcpyAsync(dk, keys, n * 4, hipMemcpyHostToDevice, s));
     const int src = pr::pairs_sort(ctx, dk, nullptr, keys_out ? dk : nullptr, di, n, s);
     if (src && src != DSORT_ESTAGE) return src;
@@ -423,14 +420,11 @@ int dsort_argsort_i32(dsort_ctx *ctx, const int32_t *keys, int32_t *keys_out, ui
 // DSORT_OPT_STAGE_TIMING off).
 int dsort_pairs_leg_ms(dsort_ctx *ctx, double ms[3]) {
     if (!ctx || !ms) return DSORT_EINVAL;
-    if (!ctx->pairs_ev_ok) return set_err(ctx, DSORT_EINVAL, "no timed pair sort on this context");
-    DSORT_HIP(ctx, hipEventSynchronize(ctx->pairs_ev[3]));
-    for (int i = 0; i < 3; ++i) {
-        float f = 0;
-        DSORT_HIP(ctx, hipEventElapsedTime(&f, ctx->pairs_ev[i], ctx->pairs_ev[i + 1]));
-        ms[i] = f;
-    }
-    return DSORT_OK;
+    const LegClock &c = ctx->pairs_clk;
+    if (!c.complete(4)) return set_err(ctx, DSORT_EINVAL, "no timed pair sort on this context");
+    int rc = c.wait_last(ctx);
+    for (int i = 0; i < 3 && !rc; ++i) rc = c.elapsed(ctx, i, i + 1, &ms[i]);
+    return rc;
 }
 
 }  // extern "C"

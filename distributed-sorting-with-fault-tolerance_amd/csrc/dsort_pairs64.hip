@@ -516,24 +516,16 @@ static int plan_argsort64(uint64_t n, int64_t kmin, int64_t kmax, int *idx_bits,
     return DSORT_OK;
 }
 
-// The legs' events of the last int64 argsort, for dsort_argsort64_leg_ms below.
-static void leg_event(dsort_ctx *ctx, hipStream_t s) {
-    if (!ctx->a64_ev_ok || ctx->a64_legs >= dsort_ctx::kA64Ev) return;
-    hipEvent_t &e = ctx->a64_ev[ctx->a64_legs];
-    ctx->a64_ev_ok = (e || hipEventCreate(&e) == hipSuccess) && hipEventRecord(e, s) == hipSuccess;
-    if (ctx->a64_ev_ok) ++ctx->a64_legs;
-}
-
 // min and max of keys[0..n), n > 0, on the host: two launches, a 16-byte copy into the pinned
 // mirror and one host wait.
 static int minmax(dsort_ctx *ctx, const int64_t *keys, size_t n, hipStream_t s, int64_t *kmin, int64_t *kmax,
                   int kc = 0) {
-    int rc = ensure(ctx, &ctx->a64_part, &ctx->a64_part_bytes, (size_t)(MAXWG + 1) * 16, "argsort min/max partials");
+    int rc = ensure(ctx, ctx->a64_part, (size_t)(MAXWG + 1) * 16, "argsort min/max partials");
     if (rc) return rc;
     if ((rc = ensure_small_host(ctx, 16))) return rc;
-    if (!ctx->a64_mm_ev && hipEventCreateWithFlags(&ctx->a64_mm_ev, hipEventDisableTiming) != hipSuccess)
+    if (!ctx->a64_mm_ev && hipEventCreateWithFlags(&ctx->a64_mm_ev.h, hipEventDisableTiming) != hipSuccess)
         return set_err(ctx, DSORT_EHIP, "hipEventCreate");
-    int64_t *part = static_cast<int64_t *>(ctx->a64_part);
+    int64_t *part = ctx->a64_part.as<int64_t>();
     const unsigned grid = grid_for(((uint64_t)n + 3) / 4);
     if (kc) {
         launch_minmax_keys(kc, grid, s, keys, (uint64_t)n, part);
@@ -543,10 +535,10 @@ static int minmax(dsort_ctx *ctx, const int64_t *keys, size_t n, hipStream_t s, 
     DSORT_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(minmax_final_kernel, dim3(1), dim3(NT), 0, s, part, (uint32_t)grid, part + 2 * MAXWG);
     DSORT_HIP(ctx, hipGetLastError());
-    DSORT_HIP(ctx, hipMemcpyAsync(ctx->small_host, part + 2 * MAXWG, 16, hipMemcpyDeviceToHost, s));
+    DSORT_HIP(ctx, hipMemcpyAsync(ctx->small_host.p, part + 2 * MAXWG, 16, hipMemcpyDeviceToHost, s));
     DSORT_HIP(ctx, hipEventRecord(ctx->a64_mm_ev, s));
     if ((rc = sync_event(ctx, ctx->a64_mm_ev, "argsort min/max read-back"))) return rc;
-    const int64_t *h = static_cast<const int64_t *>(ctx->small_host);
+    const int64_t *h = ctx->small_host.as<const int64_t>();
     *kmin = h[0];
     *kmax = h[1];
     return DSORT_OK;
@@ -580,21 +572,20 @@ int argsort64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uint32_t *
     // one bracket around the whole sequence: the arenas are shared by calls on different streams
     int rc = order_begin(ctx, s);
     if (rc) return rc;
-    rc = ensure(ctx, &ctx->pairs, &ctx->pairs_bytes, n * 8, "pair arena");
+    rc = ensure(ctx, ctx->pairs, n * 8, "pair arena");
     if (rc) return rc;
-    uint64_t *A = static_cast<uint64_t *>(ctx->pairs);
-    ctx->a64_legs = 0;
-    ctx->a64_ev_ok = ctx->ev_ok && ctx->opt.stage_timing;
+    uint64_t *A = ctx->pairs.as<uint64_t>();
+    ctx->a64_clk.start(ctx->ev_ok && ctx->opt.stage_timing);  // (the legs' events, for dsort_argsort64_leg_ms)
     ctx->a64_minmax = false;
     int b = 0, passes = 2;
     int64_t kmin = 0, kmax = 0;
-    leg_event(ctx, s);
+    ctx->a64_clk.mark(s);
     if (!ctx->opt.argsort_wide) {
         if ((rc = minmax(ctx, keys, n, s, &kmin, &kmax, kc))) return rc;
         if ((rc = plan_argsort64(n, kmin, kmax, &b, &passes)))
             return set_err(ctx, DSORT_EHIP, "argsort: the min/max reduction returned min > max");
         ctx->a64_minmax = true;
-        leg_event(ctx, s);
+        ctx->a64_clk.mark(s);
     }
     const unsigned grid = grid_for(((uint64_t)n + 3) / 4);
     int done = 0, src;
@@ -606,11 +597,11 @@ int argsort64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uint32_t *
                                b, (uint64_t)0);
         }
         DSORT_HIP(ctx, hipGetLastError());
-        leg_event(ctx, s);
+        ctx->a64_clk.mark(s);
         // DSORT_ESTAGE (the kill stage was never reached) leaves a valid output: the rest still runs
         src = inner_sort(ctx, A, n, s, &done);
         if (src && src != DSORT_ESTAGE) return src;
-        leg_event(ctx, s);
+        ctx->a64_clk.mark(s);
         if (kc) {
             launch_unpack64_keys(kc, grid, s, A, keys_out, idx_out, (uint64_t)n, (uint64_t)kmin, b);
         } else {
@@ -619,9 +610,9 @@ int argsort64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uint32_t *
         }
         DSORT_HIP(ctx, hipGetLastError());
     } else {
-        rc = ensure(ctx, &ctx->a64_b, &ctx->a64_b_bytes, n * 8, "argsort second arena");
+        rc = ensure(ctx, ctx->a64_b, n * 8, "argsort second arena");
         if (rc) return rc;
-        uint64_t *B = static_cast<uint64_t *>(ctx->a64_b);
+        uint64_t *B = ctx->a64_b.as<uint64_t>();
         if (kc) {
             launch_pack64_keys(kc, true, grid, s, keys, A, (uint64_t)n, (uint64_t)0, 0, (uint64_t)0);
         } else {
@@ -629,20 +620,20 @@ int argsort64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uint32_t *
                                (uint64_t)0);
         }
         DSORT_HIP(ctx, hipGetLastError());
-        leg_event(ctx, s);
+        ctx->a64_clk.mark(s);
         src = inner_sort(ctx, A, n, s, &done);
         if (src && src != DSORT_ESTAGE) return src;
-        leg_event(ctx, s);
+        ctx->a64_clk.mark(s);
         if (kc) {
             launch_regroup64_keys(kc, grid, s, A, keys, B, (uint64_t)n);
         } else {
             hipLaunchKernelGGL(regroup64_kernel, dim3(grid), dim3(NT), 0, s, A, keys, B, (uint64_t)n);
         }
         DSORT_HIP(ctx, hipGetLastError());
-        leg_event(ctx, s);
+        ctx->a64_clk.mark(s);
         src = inner_sort(ctx, B, n, s, &done);
         if (src && src != DSORT_ESTAGE) return src;
-        leg_event(ctx, s);
+        ctx->a64_clk.mark(s);
         if (kc) {
             launch_final64_keys(kc, grid, s, B, A, keys_out, idx_out, (uint64_t)n);
         } else {
@@ -650,7 +641,7 @@ int argsort64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, uint32_t *
         }
         DSORT_HIP(ctx, hipGetLastError());
     }
-    leg_event(ctx, s);
+    ctx->a64_clk.mark(s);
     ctx->stats.argsort_passes = passes;
     if ((rc = order_end(ctx, s))) return rc;
     if (src == DSORT_ESTAGE)
@@ -688,13 +679,6 @@ static int plan_sample_argsort64(int P, const uint64_t *first, const uint64_t *c
     return DSORT_OK;
 }
 
-static void sample_leg_event(dsort_ctx *ctx, hipStream_t s) {
-    if (!ctx->s64_ev_ok || ctx->s64_legs >= dsort_ctx::kS64Ev) return;
-    hipEvent_t &e = ctx->s64_ev[ctx->s64_legs];
-    ctx->s64_ev_ok = (e || hipEventCreate(&e) == hipSuccess) && hipEventRecord(e, s) == hipSuccess;
-    if (ctx->s64_ev_ok) ++ctx->s64_legs;
-}
-
 static int launched(dsort_ctx *ctx, const char *what) {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? DSORT_OK : hip_err(ctx, e, what);
@@ -730,9 +714,8 @@ static int sample_argsort64(dsort_ctx *ctx, const int64_t *keys, size_t n, uint6
 
     int rc = order_begin(ctx, s);
     if (rc) return fail(rc);
-    ctx->s64_legs = 0;
-    ctx->s64_ev_ok = ctx->ev_ok && ctx->opt.stage_timing;
-    sample_leg_event(ctx, s);
+    ctx->s64_clk.start(ctx->ev_ok && ctx->opt.stage_timing);  // (the legs' events, for dsort_sample_argsort64_leg_ms)
+    ctx->s64_clk.mark(s);
 
     // leg 0, the decision: every rank's range, min and max and option, and the host rule on them
     if ((rc = before_leg(0))) return rc;
@@ -782,19 +765,19 @@ static int sample_argsort64(dsort_ctx *ctx, const int64_t *keys, size_t n, uint6
         ctx->stats = fresh_stats();
         ctx->ev_mask = 0;
         ctx->kev_used = 0;
-        if (keys_out) *keys_out = static_cast<int64_t *>(ctx->s64_k);
-        *idx_out = static_cast<uint32_t *>(ctx->s64_i);
+        if (keys_out) *keys_out = ctx->s64_k.as<int64_t>();
+        *idx_out = ctx->s64_i.as<uint32_t>();
         *n_out = 0;
         return DSORT_OK;
     }
     ahead = true;
-    sample_leg_event(ctx, s);
+    ctx->s64_clk.mark(s);
     const bool wide = pl.passes == 2;
     const unsigned grid = grid_for(((uint64_t)n + 3) / 4);
 
     // the words of the first (narrow: the only) sort, positions from `first` on
-    if ((rc = ensure(ctx, &ctx->pairs, &ctx->pairs_bytes, (n ? n : 1) * 8, "pair arena"))) return fail(rc);
-    uint64_t *A = static_cast<uint64_t *>(ctx->pairs);
+    if ((rc = ensure(ctx, ctx->pairs, (n ? n : 1) * 8, "pair arena"))) return fail(rc);
+    uint64_t *A = ctx->pairs.as<uint64_t>();
     if (n) {
         if (wide)
             hipLaunchKernelGGL((pack64_kernel<true>), dim3(grid), dim3(NT), 0, s, keys, A, (uint64_t)n, (uint64_t)0, 0,
@@ -804,7 +787,7 @@ static int sample_argsort64(dsort_ctx *ctx, const int64_t *keys, size_t n, uint6
                                (uint64_t)pl.kmin, pl.b, first);
         if ((rc = launched(ctx, "pack64_kernel"))) return fail(rc);
     }
-    sample_leg_event(ctx, s);
+    ctx->s64_clk.mark(s);
 
     // leg 1.  A kill stage this sort never reaches would make it return early, DSORT_ESTAGE, with
     // the peers in the legs that follow: switched off for it and reported at the end instead.
@@ -819,29 +802,29 @@ static int sample_argsort64(dsort_ctx *ctx, const int64_t *keys, size_t n, uint6
     ahead = wide;
     if (mA && (reinterpret_cast<uintptr_t>(sa) & 15))
         return fail(set_err(ctx, DSORT_EHIP, "sample argsort: the sample sort's slice is not 16-byte aligned"));
-    sample_leg_event(ctx, s);
+    ctx->s64_clk.mark(s);
 
     size_t m = mA;
     const uint64_t *SB = nullptr, *AW = nullptr;
     if (wide) {
         // the slice is saved (the second sort's output takes its place) and split: its low words
         // are the positions of its keys
-        if ((rc = ensure(ctx, &ctx->s64_sa, &ctx->s64_sa_bytes, (mA ? mA : 1) * 8, "sample argsort saved slice")))
+        if ((rc = ensure(ctx, ctx->s64_sa, (mA ? mA : 1) * 8, "sample argsort saved slice")))
             return fail(rc);
-        if ((rc = ensure(ctx, &ctx->s64_pos, &ctx->s64_pos_bytes, (mA ? mA : 1) * 4, "sample argsort indices")))
+        if ((rc = ensure(ctx, ctx->s64_pos, (mA ? mA : 1) * 4, "sample argsort indices")))
             return fail(rc);
-        if ((rc = ensure(ctx, &ctx->s64_got, &ctx->s64_got_bytes, (mA ? mA : 1) * 8, "sample argsort gathered words")))
+        if ((rc = ensure(ctx, ctx->s64_got, (mA ? mA : 1) * 8, "sample argsort gathered words")))
             return fail(rc);
-        uint64_t *SA = static_cast<uint64_t *>(ctx->s64_sa);
-        uint32_t *pos = static_cast<uint32_t *>(ctx->s64_pos);
-        uint64_t *got = static_cast<uint64_t *>(ctx->s64_got);
+        uint64_t *SA = ctx->s64_sa.as<uint64_t>();
+        uint32_t *pos = ctx->s64_pos.as<uint32_t>();
+        uint64_t *got = ctx->s64_got.as<uint64_t>();
         const unsigned gA = grid_for(((uint64_t)mA + 3) / 4);
         if (mA) {
             hipLaunchKernelGGL(split64_kernel, dim3(gA), dim3(NT), 0, s, reinterpret_cast<const uint64_t *>(sa), SA, pos,
                                (uint64_t)mA);
             if ((rc = launched(ctx, "split64_kernel"))) return fail(rc);
         }
-        sample_leg_event(ctx, s);
+        ctx->s64_clk.mark(s);
 
         // leg 2: every rank's slice length; offA = the rank of this slice's first word in pass-A order
         if ((rc = before_leg(2))) return rc;
@@ -869,16 +852,16 @@ static int sample_argsort64(dsort_ctx *ctx, const int64_t *keys, size_t n, uint6
         if ((rc = before_leg(3))) return rc;
         rc = dsort_sample_gather_dev(ctx, keys, n, first, pos, mA, got, 8, stream);
         if (rc) return rc;
-        sample_leg_event(ctx, s);
+        ctx->s64_clk.mark(s);
 
         // the second sort's words: the high halves over the ranks in pass-A order
-        if ((rc = ensure(ctx, &ctx->pairs, &ctx->pairs_bytes, (mA ? mA : 1) * 8, "pair arena"))) return fail(rc);
-        uint64_t *B = static_cast<uint64_t *>(ctx->pairs);
+        if ((rc = ensure(ctx, ctx->pairs, (mA ? mA : 1) * 8, "pair arena"))) return fail(rc);
+        uint64_t *B = ctx->pairs.as<uint64_t>();
         if (mA) {
             hipLaunchKernelGGL(regroup_stream64_kernel, dim3(gA), dim3(NT), 0, s, got, B, (uint64_t)mA, (uint32_t)offA);
             if ((rc = launched(ctx, "regroup_stream64_kernel"))) return fail(rc);
         }
-        sample_leg_event(ctx, s);
+        ctx->s64_clk.mark(s);
 
         // leg 4
         if ((rc = before_leg(4))) return rc;
@@ -888,36 +871,36 @@ static int sample_argsort64(dsort_ctx *ctx, const int64_t *keys, size_t n, uint6
         if (rc) return rc;
         if (mB && (reinterpret_cast<uintptr_t>(sb) & 15))
             return fail(set_err(ctx, DSORT_EHIP, "sample argsort: the sample sort's slice is not 16-byte aligned"));
-        sample_leg_event(ctx, s);
-        if ((rc = ensure(ctx, &ctx->s64_pos, &ctx->s64_pos_bytes, (mB ? mB : 1) * 4, "sample argsort indices")))
+        ctx->s64_clk.mark(s);
+        if ((rc = ensure(ctx, ctx->s64_pos, (mB ? mB : 1) * 4, "sample argsort indices")))
             return fail(rc);
-        if ((rc = ensure(ctx, &ctx->s64_got, &ctx->s64_got_bytes, (mB ? mB : 1) * 8, "sample argsort gathered words")))
+        if ((rc = ensure(ctx, ctx->s64_got, (mB ? mB : 1) * 8, "sample argsort gathered words")))
             return fail(rc);
-        pos = static_cast<uint32_t *>(ctx->s64_pos);
-        got = static_cast<uint64_t *>(ctx->s64_got);
+        pos = ctx->s64_pos.as<uint32_t>();
+        got = ctx->s64_got.as<uint64_t>();
         if (mB) {
             hipLaunchKernelGGL(split64_kernel, dim3(grid_for(((uint64_t)mB + 3) / 4)), dim3(NT), 0, s,
                                reinterpret_cast<const uint64_t *>(sb), static_cast<uint64_t *>(nullptr), pos, (uint64_t)mB);
             if ((rc = launched(ctx, "split64_kernel"))) return fail(rc);
         }
-        sample_leg_event(ctx, s);
+        ctx->s64_clk.mark(s);
 
         // leg 5: every word of the slice gets its pass-A word, which rank offA' + j' of some rank holds
         if ((rc = before_leg(5))) return rc;
         rc = dsort_sample_gather_dev(ctx, SA, mA, offA, pos, mB, got, 8, stream);
         if (rc) return rc;
         ahead = false;
-        sample_leg_event(ctx, s);
+        ctx->s64_clk.mark(s);
         m = mB;
         SB = reinterpret_cast<const uint64_t *>(sb);
         AW = got;
     }
 
     // this rank's slice into the output arenas
-    if (keys_out && (rc = ensure(ctx, &ctx->s64_k, &ctx->s64_k_bytes, (m ? m : 1) * 8, "sample argsort keys"))) return rc;
-    if ((rc = ensure(ctx, &ctx->s64_i, &ctx->s64_i_bytes, (m ? m : 1) * 4, "sample argsort positions"))) return rc;
-    int64_t *ko = keys_out ? static_cast<int64_t *>(ctx->s64_k) : nullptr;
-    uint32_t *io = static_cast<uint32_t *>(ctx->s64_i);
+    if (keys_out && (rc = ensure(ctx, ctx->s64_k, (m ? m : 1) * 8, "sample argsort keys"))) return rc;
+    if ((rc = ensure(ctx, ctx->s64_i, (m ? m : 1) * 4, "sample argsort positions"))) return rc;
+    int64_t *ko = keys_out ? ctx->s64_k.as<int64_t>() : nullptr;
+    uint32_t *io = ctx->s64_i.as<uint32_t>();
     if (m) {
         const unsigned g = grid_for(((uint64_t)m + 3) / 4);
         if (wide)
@@ -927,7 +910,7 @@ static int sample_argsort64(dsort_ctx *ctx, const int64_t *keys, size_t n, uint6
                                (uint64_t)m, (uint64_t)pl.kmin, pl.b);
         if ((rc = launched(ctx, "sample argsort unpack"))) return rc;
     }
-    sample_leg_event(ctx, s);
+    ctx->s64_clk.mark(s);
     ctx->stats.argsort_passes = pl.passes;
     if ((rc = order_end(ctx, s))) return rc;
     if (keys_out) *keys_out = ko;
@@ -977,9 +960,9 @@ int dsort_sort_records_dev_i64(dsort_ctx *ctx, const int64_t *d_keys, int64_t *d
     if (n == 0) return p64::argsort64(ctx, d_keys, d_keys_out, nullptr, 0, s);  // (resets the statistics)
     int rc = order_begin(ctx, s);
     if (rc) return rc;
-    rc = ensure(ctx, &ctx->a64_idx, &ctx->a64_idx_bytes, n * 4, "record sort indices");
+    rc = ensure(ctx, ctx->a64_idx, n * 4, "record sort indices");
     if (rc) return rc;
-    uint32_t *idx = static_cast<uint32_t *>(ctx->a64_idx);
+    uint32_t *idx = ctx->a64_idx.as<uint32_t>();
     const int src = p64::argsort64(ctx, d_keys, d_keys_out, idx, n, s);
     if (src && src != DSORT_ESTAGE) return src;
     const std::string msg = ctx->err;
@@ -1014,13 +997,13 @@ int dsort_argsort_i64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, ui
     if (!ctx) return DSORT_EINVAL;
     if (int rc = p64::check_args(ctx, keys, idx, n)) return rc;
     if (n == 0) return DSORT_OK;
-    int rc = ensure(ctx, &ctx->io, &ctx->io_bytes, n * 8, "staging");
+    int rc = ensure(ctx, ctx->io, n * 8, "staging");
     if (rc) return rc;
-    rc = ensure(ctx, &ctx->io2, &ctx->io2_bytes, n * 4, "staging 2");
+    rc = ensure(ctx, ctx->io2, n * 4, "staging 2");
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    int64_t *dk = static_cast<int64_t *>(ctx->io);
-    uint32_t *di = static_cast<uint32_t *>(ctx->io2);
+    int64_t *dk = ctx->io.as<int64_t>();
+    uint32_t *di = ctx->io2.as<uint32_t>();
     DSORT_HIP(ctx, hipMemcpyAsync(dk, keys, n * 8, hipMemcpyHostToDevice, s));
     const int src = p64::argsort64(ctx, dk, keys_out ? dk : nullptr, di, n, s);
     if (src && src != DSORT_ESTAGE) return src;
@@ -1037,19 +1020,15 @@ int dsort_argsort_i64(dsort_ctx *ctx, const int64_t *keys, int64_t *keys_out, ui
 // 6; ms must hold 6).  Blocks until that call has finished; DSORT_EINVAL when it recorded none.
 int dsort_argsort64_leg_ms(dsort_ctx *ctx, double ms[6], int *legs) {
     if (!ctx || !ms || !legs) return DSORT_EINVAL;
+    const LegClock &c = ctx->a64_clk;
     const int first = ctx->a64_minmax ? 0 : 1;  // without the reduction the events start at the pack
-    const int nl = ctx->a64_legs - 1 + first;
-    if (!ctx->a64_ev_ok || (nl != 4 && nl != 6))
-        return set_err(ctx, DSORT_EINVAL, "no timed int64 argsort on this context");
-    DSORT_HIP(ctx, hipEventSynchronize(ctx->a64_ev[ctx->a64_legs - 1]));
+    const int nl = c.count() - 1 + first;
+    if (!c.count() || (nl != 4 && nl != 6)) return set_err(ctx, DSORT_EINVAL, "no timed int64 argsort on this context");
+    int rc = c.wait_last(ctx);
     ms[0] = 0;
-    for (int i = first; i < nl; ++i) {
-        float f = 0;
-        DSORT_HIP(ctx, hipEventElapsedTime(&f, ctx->a64_ev[i - first], ctx->a64_ev[i - first + 1]));
-        ms[i] = f;
-    }
+    for (int i = first; i < nl && !rc; ++i) rc = c.elapsed(ctx, i - first, i - first + 1, &ms[i]);
     *legs = nl;
-    return DSORT_OK;
+    return rc;
 }
 
 // The same for the last dsort_sample_argsort_dev_i64 (scripts/bench_pairs.py --sample-i64); the time
@@ -1059,17 +1038,13 @@ int dsort_argsort64_leg_ms(dsort_ctx *ctx, double ms[6], int *legs) {
 // split, final gather, final.  ms must hold 10.  DSORT_EINVAL when the call recorded none.
 int dsort_sample_argsort64_leg_ms(dsort_ctx *ctx, double ms[10], int *legs) {
     if (!ctx || !ms || !legs) return DSORT_EINVAL;
-    const int nl = ctx->s64_legs - 1;
-    if (!ctx->s64_ev_ok || (nl != 4 && nl != 10))
-        return set_err(ctx, DSORT_EINVAL, "no timed int64 sample argsort on this context");
-    DSORT_HIP(ctx, hipEventSynchronize(ctx->s64_ev[nl]));
-    for (int i = 0; i < nl; ++i) {
-        float f = 0;
-        DSORT_HIP(ctx, hipEventElapsedTime(&f, ctx->s64_ev[i], ctx->s64_ev[i + 1]));
-        ms[i] = f;
-    }
+    const LegClock &c = ctx->s64_clk;
+    const int nl = c.count() - 1;
+    if (nl != 4 && nl != 10) return set_err(ctx, DSORT_EINVAL, "no timed int64 sample argsort on this context");
+    int rc = c.wait_last(ctx);
+    for (int i = 0; i < nl && !rc; ++i) rc = c.elapsed(ctx, i, i + 1, &ms[i]);
     *legs = nl;
-    return DSORT_OK;
+    return rc;
 }
 
 }  // extern "C"

@@ -420,12 +420,12 @@ __global__ void __launch_bounds__(NT) parse_kernel(const char *__restrict__ text
 // total bytes / tokens (the scan's), red[2] = first error position (~0: none).
 static int text_prepare(dsort_ctx *ctx, uint64_t ntiles, hipStream_t s, uint32_t **cnt, uint64_t **pref) {
     const size_t cbytes = (ntiles * sizeof(uint32_t) + 255) & ~(size_t)255;
-    int rc = ensure(ctx, &ctx->text_status, &ctx->text_status_bytes, cbytes + ntiles * sizeof(uint64_t),
+    int rc = ensure(ctx, ctx->text_status, cbytes + ntiles * sizeof(uint64_t),
                     "text tile tables");
     if (rc) return rc;
-    *cnt = static_cast<uint32_t *>(ctx->text_status);
-    *pref = reinterpret_cast<uint64_t *>(static_cast<char *>(ctx->text_status) + cbytes);
-    DSORT_HIP(ctx, hipMemsetAsync(static_cast<char *>(ctx->red) + 16, 0xFF, 8, s));
+    *cnt = ctx->text_status.as<uint32_t>();
+    *pref = reinterpret_cast<uint64_t *>(ctx->text_status.as<char>() + cbytes);
+    DSORT_HIP(ctx, hipMemsetAsync(ctx->red.as<char>() + 16, 0xFF, 8, s));
     return DSORT_OK;
 }
 
@@ -449,15 +449,15 @@ int dsort_format_text_dev_i32(dsort_ctx *ctx, const int32_t *d_keys, size_t n, c
     uint64_t *pref;
     int rc = text_prepare(ctx, ntiles, s, &cnt, &pref);
     if (rc) return rc;
-    uint64_t *red = static_cast<uint64_t *>(ctx->red);
+    uint64_t *red = ctx->red.as<uint64_t>();
     hipLaunchKernelGGL(tx::format_count_kernel, dim3((unsigned)ntiles), dim3(tx::NT), 0, s, d_keys, (uint64_t)n, cnt);
     hipLaunchKernelGGL(tx::tile_scan_kernel, dim3(1), dim3(tx::SCAN_T), 0, s, cnt, pref, (uint32_t)ntiles, red + 1);
     hipLaunchKernelGGL(tx::format_kernel, dim3((unsigned)ntiles), dim3(tx::NT), 0, s, d_keys,
                        (uint64_t)n, d_text, (uint64_t)cap, static_cast<const uint64_t *>(pref));
     DSORT_HIP(ctx, hipGetLastError());
-    DSORT_HIP(ctx, hipMemcpyAsync(ctx->red_host, ctx->red, 24, hipMemcpyDeviceToHost, s));
+    DSORT_HIP(ctx, hipMemcpyAsync(ctx->red_host.p, ctx->red.p, 24, hipMemcpyDeviceToHost, s));
     DSORT_HIP(ctx, hipStreamSynchronize(s));
-    *out_len = ctx->red_host[1];
+    *out_len = ctx->red_host.as<uint64_t>()[1];
     return DSORT_OK;
 }
 
@@ -476,19 +476,19 @@ int dsort_parse_text_dev_i32(dsort_ctx *ctx, const char *d_text, size_t len, int
     uint64_t *pref;
     int rc = text_prepare(ctx, ntiles, s, &cnt, &pref);
     if (rc) return rc;
-    uint64_t *red = static_cast<uint64_t *>(ctx->red);
+    uint64_t *red = ctx->red.as<uint64_t>();
     hipLaunchKernelGGL(tx::parse_count_kernel, dim3((unsigned)ntiles), dim3(tx::NT), 0, s, d_text, (uint64_t)len, cnt);
     hipLaunchKernelGGL(tx::tile_scan_kernel, dim3(1), dim3(tx::SCAN_T), 0, s, cnt, pref, (uint32_t)ntiles, red + 1);
     hipLaunchKernelGGL(tx::parse_kernel, dim3((unsigned)ntiles), dim3(tx::NT), 0, s, d_text,
                        (uint64_t)len, d_keys, (uint64_t)cap, static_cast<const uint64_t *>(pref),
                        reinterpret_cast<unsigned long long *>(red + 2));
     DSORT_HIP(ctx, hipGetLastError());
-    DSORT_HIP(ctx, hipMemcpyAsync(ctx->red_host, ctx->red, 24, hipMemcpyDeviceToHost, s));
+    DSORT_HIP(ctx, hipMemcpyAsync(ctx->red_host.p, ctx->red.p, 24, hipMemcpyDeviceToHost, s));
     DSORT_HIP(ctx, hipStreamSynchronize(s));
-    *n_out = ctx->red_host[1];
-    if (ctx->red_host[2] != ~0ull)
+    *n_out = ctx->red_host.as<uint64_t>()[1];
+    if (ctx->red_host.as<uint64_t>()[2] != ~0ull)
         return set_err(ctx, DSORT_EINVAL,
-                       "not an integer token at byte " + std::to_string(ctx->red_host[2]));
+                       "not an integer token at byte " + std::to_string(ctx->red_host.as<uint64_t>()[2]));
     return DSORT_OK;
 }
 
@@ -500,17 +500,17 @@ int dsort_parse_text_i32(dsort_ctx *ctx, const char *text, size_t len, int32_t *
         return set_err(ctx, DSORT_EINVAL, "null argument");
     *n_out = 0;
     if (!len) return DSORT_OK;
-    int rc = ensure(ctx, &ctx->io, &ctx->io_bytes, len, "text staging");
-    if (!rc) rc = ensure(ctx, &ctx->io2, &ctx->io2_bytes, (cap ? cap : 1) * sizeof(int32_t), "key staging");
+    int rc = ensure(ctx, ctx->io, len, "text staging");
+    if (!rc) rc = ensure(ctx, ctx->io2, (cap ? cap : 1) * sizeof(int32_t), "key staging");
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    DSORT_HIP(ctx, hipMemcpyAsync(ctx->io, text, len, hipMemcpyHostToDevice, s));
+    DSORT_HIP(ctx, hipMemcpyAsync(ctx->io.p, text, len, hipMemcpyHostToDevice, s));
     size_t cnt = 0;
-    rc = dsort_parse_text_dev_i32(ctx, static_cast<const char *>(ctx->io), len,
-                                  static_cast<int32_t *>(ctx->io2), cap, &cnt, s);
+    rc = dsort_parse_text_dev_i32(ctx, ctx->io.as<const char>(), len,
+                                  ctx->io2.as<int32_t>(), cap, &cnt, s);
     if (rc) return rc;
     const size_t got = cnt < cap ? cnt : cap;
-    if (got) DSORT_HIP(ctx, hipMemcpyAsync(keys, ctx->io2, got * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (got) DSORT_HIP(ctx, hipMemcpyAsync(keys, ctx->io2.p, got * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     DSORT_HIP(ctx, hipStreamSynchronize(s));
     *n_out = cnt;
     return DSORT_OK;
@@ -522,17 +522,17 @@ int dsort_format_text_i32(dsort_ctx *ctx, const int32_t *keys, size_t n, char *t
         return set_err(ctx, DSORT_EINVAL, "null argument");
     *len_out = 0;
     if (!n) return DSORT_OK;
-    int rc = ensure(ctx, &ctx->io, &ctx->io_bytes, n * sizeof(int32_t), "key staging");
-    if (!rc) rc = ensure(ctx, &ctx->io2, &ctx->io2_bytes, 12 * n, "text staging");
+    int rc = ensure(ctx, ctx->io, n * sizeof(int32_t), "key staging");
+    if (!rc) rc = ensure(ctx, ctx->io2, 12 * n, "text staging");
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    DSORT_HIP(ctx, hipMemcpyAsync(ctx->io, keys, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    DSORT_HIP(ctx, hipMemcpyAsync(ctx->io.p, keys, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
     size_t ln = 0;
-    rc = dsort_format_text_dev_i32(ctx, static_cast<const int32_t *>(ctx->io), n,
-                                   static_cast<char *>(ctx->io2), 12 * n, &ln, s);
+    rc = dsort_format_text_dev_i32(ctx, ctx->io.as<const int32_t>(), n,
+                                   ctx->io2.as<char>(), 12 * n, &ln, s);
     if (rc) return rc;
     if (ln > cap) return set_err(ctx, DSORT_EINVAL, "text buffer too small");
-    DSORT_HIP(ctx, hipMemcpyAsync(text, ctx->io2, ln, hipMemcpyDeviceToHost, s));
+    DSORT_HIP(ctx, hipMemcpyAsync(text, ctx->io2.p, ln, hipMemcpyDeviceToHost, s));
     DSORT_HIP(ctx, hipStreamSynchronize(s));
     *len_out = ln;
     return DSORT_OK;

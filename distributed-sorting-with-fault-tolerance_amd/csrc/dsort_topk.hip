@@ -427,11 +427,7 @@ static void launch_compact(int kc, unsigned G, hipStream_t s, const uint32_t *ke
 
 // The legs' events of the last select (dsort_topk_leg_ms), recorded only when asked for
 // (dsort_topk_leg_timing): 2 p and 2 p + 1 around pass p's histogram, 12 and 13 around the compaction.
-static bool leg_event(dsort_ctx *ctx, int i, hipStream_t s) {
-    if (!ctx->tk_timing) return false;
-    if (!ctx->tk_ev[i] && hipEventCreate(&ctx->tk_ev[i]) != hipSuccess) return false;
-    return hipEventRecord(ctx->tk_ev[i], s) == hipSuccess;
-}
+constexpr int EV_COMPACT = 12, EV_COUNT = 14;
 
 // The select itself: the k (1 <= k <= n) winners of keys[0..n) in ascending position into out_w
 // (and, 8-byte keys, out_p), k slots each; positions count from posbase.  Asynchronous on s, inside
@@ -442,22 +438,23 @@ static int select(dsort_ctx *ctx, const void *d_keys, size_t n, size_t k, KeySpe
     unsigned G = 0;
     uint64_t chunk = 0;
     select_grid((uint64_t)n, W, &G, &chunk);
-    int rc = ensure(ctx, &ctx->tk_rows, &ctx->tk_rows_bytes, (size_t)G * NB * 4, "top-k histogram rows");
+    int rc = ensure(ctx, ctx->tk_rows, (size_t)G * NB * 4, "top-k histogram rows");
     if (rc) return rc;
-    rc = ensure(ctx, &ctx->tk_small, &ctx->tk_small_bytes, SMALL_BYTES, "top-k tables");
+    rc = ensure(ctx, ctx->tk_small, SMALL_BYTES, "top-k tables");
     if (rc) return rc;
-    char *sm = static_cast<char *>(ctx->tk_small);
+    char *sm = ctx->tk_small.as<char>();
     State *st = reinterpret_cast<State *>(sm);
     uint32_t *part = reinterpret_cast<uint32_t *>(sm + OFF_PART);
     uint32_t *less = reinterpret_cast<uint32_t *>(sm + OFF_LESS);
     uint32_t *eq = reinterpret_cast<uint32_t *>(sm + OFF_EQ);
     uint32_t *quota = reinterpret_cast<uint32_t *>(sm + OFF_QUOTA);
     uint64_t *off = reinterpret_cast<uint64_t *>(sm + OFF_OFF);
-    uint32_t *rows = static_cast<uint32_t *>(ctx->tk_rows);
+    uint32_t *rows = ctx->tk_rows.as<uint32_t>();
     const uint32_t *keys = static_cast<const uint32_t *>(d_keys);
     const int RS = (int)((G + RSL - 1) / RSL), passes = digits_of(W), bits = 8 * W;
+    LegClock &clk = ctx->tk_clk;
+    clk.start(ctx->tk_timing);
     ctx->tk_passes = 0;
-    bool ev = true;
     hipLaunchKernelGGL(topk_init_kernel, dim3(1), dim3(1), 0, s, st, (uint64_t)k);
     DSORT_HIP(ctx, hipGetLastError());
     for (int p = 0; p < passes; ++p) {
@@ -465,13 +462,13 @@ static int select(dsort_ctx *ctx, const void *d_keys, size_t n, size_t k, KeySpe
         const int shift = hi_shift > DB ? hi_shift - DB : 0;
         const uint32_t mask = (1u << (hi_shift - shift)) - 1u;
         const bool first = p == 0, last = p == passes - 1;
-        ev = leg_event(ctx, 2 * p, s) && ev;
+        clk.mark_at(2 * p, s);
         if (W == 4)
             launch_hist<4>(ks.kc, first, G, s, keys, (uint64_t)n, chunk, st, shift, mask, hi_shift, rows);
         else
             launch_hist<8>(ks.kc, first, G, s, keys, (uint64_t)n, chunk, st, shift, mask, hi_shift, rows);
         DSORT_HIP(ctx, hipGetLastError());
-        ev = leg_event(ctx, 2 * p + 1, s) && ev;
+        clk.mark_at(2 * p + 1, s);
         hipLaunchKernelGGL(topk_colsum_kernel, dim3(NB / NT, RS), dim3(NT), 0, s, rows, (int)G, part);
         DSORT_HIP(ctx, hipGetLastError());
         hipLaunchKernelGGL(topk_pick_kernel, dim3(1), dim3(NT), 0, s, part, RS, st, shift);
@@ -487,14 +484,14 @@ static int select(dsort_ctx *ctx, const void *d_keys, size_t n, size_t k, KeySpe
     }
     hipLaunchKernelGGL(topk_offsets_kernel, dim3(1), dim3(NT), 0, s, less, eq, (int)G, st, quota, off);
     DSORT_HIP(ctx, hipGetLastError());
-    ev = leg_event(ctx, 12, s) && ev;
+    clk.mark_at(EV_COMPACT, s);
     if (W == 4)
         launch_compact<4>(ks.kc, G, s, keys, (uint64_t)n, chunk, st, quota, off, posbase, (uint64_t)k, out_w, out_p);
     else
         launch_compact<8>(ks.kc, G, s, keys, (uint64_t)n, chunk, st, quota, off, posbase, (uint64_t)k, out_w, out_p);
     DSORT_HIP(ctx, hipGetLastError());
-    ev = leg_event(ctx, 13, s) && ev;
-    ctx->tk_passes = ev ? passes : 0;
+    clk.mark_at(EV_COMPACT + 1, s);
+    ctx->tk_passes = clk.complete(EV_COUNT) ? passes : 0;
     return DSORT_OK;
 }
 
@@ -535,11 +532,11 @@ static int topk_dev(dsort_ctx *ctx, const void *d_keys, size_t n, size_t k, KeyS
     std::string msg;
     if (path == 2) {
         // the existing argsort into arenas of the context, and its first k
-        rc = ensure(ctx, &ctx->a64_idx, &ctx->a64_idx_bytes, n * 4, "top-k indices");
+        rc = ensure(ctx, ctx->a64_idx, n * 4, "top-k indices");
         if (rc) return rc;
-        if (d_keys_out && (rc = ensure(ctx, &ctx->tk_ck, &ctx->tk_ck_bytes, n * W, "top-k sorted keys"))) return rc;
-        uint32_t *idx = static_cast<uint32_t *>(ctx->a64_idx);
-        void *ko = d_keys_out ? ctx->tk_ck : nullptr;
+        if (d_keys_out && (rc = ensure(ctx, ctx->tk_ck, n * W, "top-k sorted keys"))) return rc;
+        uint32_t *idx = ctx->a64_idx.as<uint32_t>();
+        void *ko = d_keys_out ? ctx->tk_ck.p : nullptr;
         src = W == 4 ? pr::pairs_sort(ctx, static_cast<const int32_t *>(d_keys), nullptr, static_cast<int32_t *>(ko),
                                       idx, n, s, ks.kc)
                      : p64::argsort64(ctx, static_cast<const int64_t *>(d_keys), static_cast<int64_t *>(ko), idx, n, s,
@@ -549,19 +546,19 @@ static int topk_dev(dsort_ctx *ctx, const void *d_keys, size_t n, size_t k, KeyS
         if (d_keys_out) DSORT_HIP(ctx, hipMemcpyAsync(d_keys_out, ko, k * W, hipMemcpyDeviceToDevice, s));
         DSORT_HIP(ctx, hipMemcpyAsync(d_idx_out, idx, k * 4, hipMemcpyDeviceToDevice, s));
     } else if (W == 4) {
-        rc = ensure(ctx, &ctx->pairs, &ctx->pairs_bytes, k * 8, "pair arena");
+        rc = ensure(ctx, ctx->pairs, k * 8, "pair arena");
         if (rc) return rc;
-        uint64_t *packed = static_cast<uint64_t *>(ctx->pairs);
+        uint64_t *packed = ctx->pairs.as<uint64_t>();
         if ((rc = select(ctx, d_keys, n, k, ks, 0, s, packed, nullptr))) return rc;
         if ((rc = finish4(ctx, packed, k, k, ks, d_keys_out, d_idx_out, s, &src))) return rc;
         msg = ctx->err;
     } else {
-        rc = ensure(ctx, &ctx->tk_ck, &ctx->tk_ck_bytes, k * 8, "top-k candidate keys");
+        rc = ensure(ctx, ctx->tk_ck, k * 8, "top-k candidate keys");
         if (rc) return rc;
-        if ((rc = ensure(ctx, &ctx->tk_cp, &ctx->tk_cp_bytes, k * 4, "top-k candidate positions"))) return rc;
-        if ((rc = ensure(ctx, &ctx->a64_idx, &ctx->a64_idx_bytes, k * 4, "top-k candidate order"))) return rc;
-        uint64_t *ck = static_cast<uint64_t *>(ctx->tk_ck);
-        uint32_t *cp = static_cast<uint32_t *>(ctx->tk_cp), *ord = static_cast<uint32_t *>(ctx->a64_idx);
+        if ((rc = ensure(ctx, ctx->tk_cp, k * 4, "top-k candidate positions"))) return rc;
+        if ((rc = ensure(ctx, ctx->a64_idx, k * 4, "top-k candidate order"))) return rc;
+        uint64_t *ck = ctx->tk_ck.as<uint64_t>();
+        uint32_t *cp = ctx->tk_cp.as<uint32_t>(), *ord = ctx->a64_idx.as<uint32_t>();
         if ((rc = select(ctx, d_keys, n, k, ks, 0, s, ck, cp))) return rc;
         // stable over candidates in ascending position: equal keys stay in position order
         src = p64::argsort64(ctx, reinterpret_cast<const int64_t *>(ck), static_cast<int64_t *>(d_keys_out), ord, k, s,
@@ -639,21 +636,21 @@ static int sample_topk(dsort_ctx *ctx, const void *d_keys, size_t n_local, uint6
     for (int r = 0; r < P; ++r) scnt[r] = cm;
 
     // this rank's candidates
-    rc = ensure(ctx, &ctx->tk_ck, &ctx->tk_ck_bytes, (cm ? cm : 1) * 8, "top-k candidate keys");
+    rc = ensure(ctx, ctx->tk_ck, (cm ? cm : 1) * 8, "top-k candidate keys");
     if (rc) return rc;
-    if (W == 8 && (rc = ensure(ctx, &ctx->tk_cp, &ctx->tk_cp_bytes, (cm ? cm : 1) * 4, "top-k candidate positions")))
+    if (W == 8 && (rc = ensure(ctx, ctx->tk_cp, (cm ? cm : 1) * 4, "top-k candidate positions")))
         return rc;
-    uint64_t *ck = static_cast<uint64_t *>(ctx->tk_ck);
-    uint32_t *cp = static_cast<uint32_t *>(ctx->tk_cp);
+    uint64_t *ck = ctx->tk_ck.as<uint64_t>();
+    uint32_t *cp = ctx->tk_cp.as<uint32_t>();
     if (cm && (rc = select(ctx, d_keys, n_local, (size_t)cm, ks, (uint32_t)first, s, ck, W == 8 ? cp : nullptr)))
         return rc;
 
     int src = DSORT_OK;
     std::string msg;
     if (W == 4) {
-        rc = ensure(ctx, &ctx->pairs, &ctx->pairs_bytes, M * 8, "pair arena");
+        rc = ensure(ctx, ctx->pairs, M * 8, "pair arena");
         if (rc) return rc;
-        uint64_t *packed = static_cast<uint64_t *>(ctx->pairs);
+        uint64_t *packed = ctx->pairs.as<uint64_t>();
         rc = alltoallv(ctx, A2av{ck, scnt.data(), soff.data(), cm, packed, rcnt.data(), roff.data(), M, 8, ncclUint64}, s,
                        deadline, "sample top-k candidate all-to-all", "sample top-k candidate all-to-all (staging)");
         if (rc) return rc;
@@ -661,13 +658,13 @@ static int sample_topk(dsort_ctx *ctx, const void *d_keys, size_t n_local, uint6
         if ((rc = finish4(ctx, packed, (size_t)M, k, ks, d_keys_out, d_idx_out, s, &src))) return rc;
         msg = ctx->err;
     } else {
-        rc = ensure(ctx, &ctx->tk_rk, &ctx->tk_rk_bytes, M * 8, "top-k candidates received");
+        rc = ensure(ctx, ctx->tk_rk, M * 8, "top-k candidates received");
         if (rc) return rc;
-        if ((rc = ensure(ctx, &ctx->tk_rp, &ctx->tk_rp_bytes, M * 4, "top-k positions received"))) return rc;
-        if ((rc = ensure(ctx, &ctx->a64_idx, &ctx->a64_idx_bytes, M * 4, "top-k candidate order"))) return rc;
-        if (d_keys_out && (rc = ensure(ctx, &ctx->tk_sk, &ctx->tk_sk_bytes, M * 8, "top-k sorted candidates"))) return rc;
-        uint64_t *rk = static_cast<uint64_t *>(ctx->tk_rk);
-        uint32_t *rp = static_cast<uint32_t *>(ctx->tk_rp), *ord = static_cast<uint32_t *>(ctx->a64_idx);
+        if ((rc = ensure(ctx, ctx->tk_rp, M * 4, "top-k positions received"))) return rc;
+        if ((rc = ensure(ctx, ctx->a64_idx, M * 4, "top-k candidate order"))) return rc;
+        if (d_keys_out && (rc = ensure(ctx, ctx->tk_sk, M * 8, "top-k sorted candidates"))) return rc;
+        uint64_t *rk = ctx->tk_rk.as<uint64_t>();
+        uint32_t *rp = ctx->tk_rp.as<uint32_t>(), *ord = ctx->a64_idx.as<uint32_t>();
         rc = alltoallv(ctx, A2av{ck, scnt.data(), soff.data(), cm, rk, rcnt.data(), roff.data(), M, 8, ncclUint64}, s,
                        deadline, "sample top-k key all-to-all", "sample top-k key all-to-all (staging)");
         if (rc) return rc;
@@ -675,7 +672,7 @@ static int sample_topk(dsort_ctx *ctx, const void *d_keys, size_t n_local, uint6
                        deadline, "sample top-k position all-to-all", "sample top-k position all-to-all (staging)");
         if (rc) return rc;
         call.finished();
-        int64_t *sk = d_keys_out ? static_cast<int64_t *>(ctx->tk_sk) : nullptr;
+        int64_t *sk = d_keys_out ? ctx->tk_sk.as<int64_t>() : nullptr;
         src = p64::argsort64(ctx, reinterpret_cast<const int64_t *>(rk), sk, ord, (size_t)M, s, ks.kc);
         if (src && src != DSORT_ESTAGE) return src;
         msg = ctx->err;
@@ -725,15 +722,15 @@ int dsort_topk_keys(dsort_ctx *ctx, const void *keys, size_t n, size_t k, int ke
     if ((n && !keys) || (k && !idx)) return set_err(ctx, DSORT_EINVAL, "null argument");
     if (k == 0) return DSORT_OK;
     const size_t W = (size_t)ks.bytes, idx_bytes = (k * 4 + 15) & ~(size_t)15;
-    int rc = ensure(ctx, &ctx->io, &ctx->io_bytes, n * W, "staging");
+    int rc = ensure(ctx, ctx->io, n * W, "staging");
     if (rc) return rc;
-    rc = ensure(ctx, &ctx->io2, &ctx->io2_bytes, idx_bytes + k * W, "staging 2");
+    rc = ensure(ctx, ctx->io2, idx_bytes + k * W, "staging 2");
     if (rc) return rc;
     hipStream_t s = ctx->stream;
-    uint32_t *di = static_cast<uint32_t *>(ctx->io2);
-    void *dk = static_cast<char *>(ctx->io2) + idx_bytes;
-    DSORT_HIP(ctx, hipMemcpyAsync(ctx->io, keys, n * W, hipMemcpyHostToDevice, s));
-    const int src = tk::topk_dev(ctx, ctx->io, n, k, ks, keys_out ? dk : nullptr, di, nullptr);
+    uint32_t *di = ctx->io2.as<uint32_t>();
+    void *dk = ctx->io2.as<char>() + idx_bytes;
+    DSORT_HIP(ctx, hipMemcpyAsync(ctx->io.p, keys, n * W, hipMemcpyHostToDevice, s));
+    const int src = tk::topk_dev(ctx, ctx->io.p, n, k, ks, keys_out ? dk : nullptr, di, nullptr);
     if (src && src != DSORT_ESTAGE) return src;
     if (keys_out) DSORT_HIP(ctx, hipMemcpyAsync(keys_out, dk, k * W, hipMemcpyDeviceToHost, s));
     DSORT_HIP(ctx, hipMemcpyAsync(idx, di, k * 4, hipMemcpyDeviceToHost, s));
@@ -770,16 +767,12 @@ int dsort_topk_leg_timing(dsort_ctx *ctx, int on) {
 int dsort_topk_leg_ms(dsort_ctx *ctx, double hist_ms[6], int *passes, double *compact_ms) {
     if (!ctx || !hist_ms || !passes || !compact_ms) return DSORT_EINVAL;
     if (!ctx->tk_passes) return set_err(ctx, DSORT_EINVAL, "no timed top-k select on this context");
-    DSORT_HIP(ctx, hipEventSynchronize(ctx->tk_ev[13]));
-    float f = 0;
-    for (int p = 0; p < ctx->tk_passes; ++p) {
-        DSORT_HIP(ctx, hipEventElapsedTime(&f, ctx->tk_ev[2 * p], ctx->tk_ev[2 * p + 1]));
-        hist_ms[p] = f;
-    }
-    DSORT_HIP(ctx, hipEventElapsedTime(&f, ctx->tk_ev[12], ctx->tk_ev[13]));
-    *compact_ms = f;
+    const LegClock &c = ctx->tk_clk;
+    int rc = c.wait_last(ctx);
+    for (int p = 0; p < ctx->tk_passes && !rc; ++p) rc = c.elapsed(ctx, 2 * p, 2 * p + 1, &hist_ms[p]);
+    if (!rc) rc = c.elapsed(ctx, tk::EV_COMPACT, tk::EV_COMPACT + 1, compact_ms);
     *passes = ctx->tk_passes;
-    return DSORT_OK;
+    return rc;
 }
 
 }  // extern "C"

@@ -1550,40 +1550,15 @@ static std::vector<int> plan_passes(const dsort_opts &opt, uint64_t runs) {
     return out;
 }
 
-// Stage event i of a timed sort (dsort_internal.h: ctx->ev): 7 / 8 around the tile sort kernel
-// (dsort_stats.tile_sort_kernel_ms, partition_ms), 9 / 10 the first-level histogram, 11 / 12 the
-// first-level scatter, 13 / 14 the second-level partition.
-// Every stage boundary of the outermost sort also opens / closes a roctx range on the host thread
-// (rocprofv3 --marker-trace shows when each stage was enqueued; the device times are the events'):
-// dsort:histogram, dsort:scatter, dsort:second-level, dsort:tile-sort.
-static void stage_range(const dsort_ctx *ctx, int i) {
-    if (ctx->nested) return;
-    switch (i) {
-        case 9: roctxRangePushA("dsort:histogram"); break;
-        case 11: roctxRangePushA("dsort:scatter"); break;
-        case 13: roctxRangePushA("dsort:second-level"); break;
-        case 7: roctxRangePushA("dsort:tile-sort"); break;
-        case 10: case 12: case 14: case 8: roctxRangePop(); break;
-        default: break;
-    }
-}
-static int stage_event(dsort_ctx *ctx, hipStream_t s, bool timed, int i) {
-    if (timed) stage_range(ctx, i);
-    if (!timed || !ctx->ev_ok) return DSORT_OK;
-    if (i == 1 || i == 7 || i == 8 || i == 13 || i == 14) i += ctx->ev_off;
-    DSORT_HIP(ctx, hipEventRecord(ctx->ev[i], s));
-    ctx->ev_mask |= 1u << i;
-    return DSORT_OK;
-}
+// The stage events of a timed sort (dsort_internal.h: StageEv, stage_event).  Those of the tile sort
+// and the second level go kWave0Offset higher while the bucket exchange's first wave runs them.
+static StageEv wave_ev(const dsort_ctx *ctx, StageEv e) { return StageEv(e + ctx->ev_off); }
 static int tile_sort_event(dsort_ctx *ctx, hipStream_t s, bool timed, int which) {
-    return stage_event(ctx, s, timed, 7 + which);
+    return stage_event(ctx, s, timed, wave_ev(ctx, which ? kEvTile1 : kEvTile0));
 }
 // The last event of a timed sort (ctx->ev_done: the bucket exchange's waves move it).
 static int sort_done_event(dsort_ctx *ctx, hipStream_t s, bool timed) {
-    if (!timed || !ctx->ev_ok) return DSORT_OK;
-    DSORT_HIP(ctx, hipEventRecord(ctx->ev[ctx->ev_done], s));
-    ctx->ev_mask |= 1u << ctx->ev_done;
-    return DSORT_OK;
+    return stage_event(ctx, s, timed, StageEv(ctx->ev_done));
 }
 
 // The tile sort of `grid` tiles (an upper bound when the count lives on the device): the bin
@@ -1596,9 +1571,9 @@ constexpr uint32_t kFallbackWgs = 512;  // two workgroups per CU
 template <typename T, bool GATHER, int W>
 static int tile_sort_begin(dsort_ctx *ctx, const T *in, T *out, uint64_t n, const uint4 *tiles, const uint32_t *ntiles,
                            const sb::Gather &ga, uint32_t grid, uint32_t cap, hipStream_t s) {
-    int rc = ensure(ctx, &ctx->tfb, &ctx->tfb_bytes, ((size_t)cap + 1) * 4, "tile fallback list");
+    int rc = ensure(ctx, ctx->tfb, ((size_t)cap + 1) * 4, "tile fallback list");
     if (rc) return rc;
-    uint32_t *fb = static_cast<uint32_t *>(ctx->tfb), *nfb = fb + cap;
+    uint32_t *fb = ctx->tfb.as<uint32_t>(), *nfb = fb + cap;
     DSORT_HIP(ctx, hipMemsetAsync(nfb, 0, 4, s));
     if (grid)
         hipLaunchKernelGGL((bin_sort_kernel<T, GATHER, W>), dim3(grid), dim3(64 * W), 0, s, in, out, n, tiles, ntiles, ga, fb,
@@ -1609,7 +1584,7 @@ static int tile_sort_begin(dsort_ctx *ctx, const T *in, T *out, uint64_t n, cons
 template <typename T, bool GATHER, int W>
 static int tile_sort_more(dsort_ctx *ctx, const T *in, T *out, uint64_t n, const uint4 *tiles, const uint32_t *ntiles,
                           const sb::Gather &ga, uint32_t toff, uint32_t grid, uint32_t cap, hipStream_t s) {
-    uint32_t *fb = static_cast<uint32_t *>(ctx->tfb), *nfb = fb + cap;
+    uint32_t *fb = ctx->tfb.as<uint32_t>(), *nfb = fb + cap;
     if (grid)
         hipLaunchKernelGGL((bin_sort_kernel<T, GATHER, W>), dim3(grid), dim3(64 * W), 0, s, in, out, n, tiles, ntiles, ga, fb,
                            nfb, toff);
@@ -1619,7 +1594,7 @@ static int tile_sort_more(dsort_ctx *ctx, const T *in, T *out, uint64_t n, const
 template <typename T, bool GATHER, int W>
 static int tile_sort_end(dsort_ctx *ctx, const T *in, T *out, uint64_t n, const uint4 *tiles, const uint32_t *ntiles,
                          const sb::Gather &ga, uint32_t tiles_total, uint32_t cap, hipStream_t s) {
-    const uint32_t *fb = static_cast<const uint32_t *>(ctx->tfb), *nfb = fb + cap;
+    const uint32_t *fb = ctx->tfb.as<const uint32_t>(), *nfb = fb + cap;
     // the declined tiles: a grid of at most one round of workgroups over the chip walks the
     // list, whose length stays on the device (round 2 read it back: the host waited for the
     // bin sort, and the GPU idled about 70 us per sort until the next work arrived)
@@ -1666,10 +1641,10 @@ static int tile_sort(dsort_ctx *ctx, const T *in, T *out, uint64_t n, const uint
 template <typename T, bool REG>
 static int launch_pass_w(dsort_ctx *ctx, const T *src, T *dst, const PassDesc &pd, int logf,
                          uint64_t ntiles, hipStream_t s, bool timed) {
-    int rc = ensure(ctx, &ctx->splits, &ctx->splits_bytes,
+    int rc = ensure(ctx, ctx->splits,
                     (size_t)(ntiles + 1) * (size_t)(1 << logf) * sizeof(uint32_t), "split vectors");
     if (rc) return rc;
-    uint32_t *sp = static_cast<uint32_t *>(ctx->splits);
+    uint32_t *sp = ctx->splits.as<uint32_t>();
     constexpr int TN = MTNOM_OF<T>;
     hipLaunchKernelGGL((partk_kernel<T, REG>), dim3((unsigned)ceil_div(ntiles, 4)), dim3(256), 0, s, src, pd,
                        TN, MSLACK_OF<T>, sp, ntiles);
@@ -1768,11 +1743,11 @@ static std::vector<size_t> sub_tile_runs(uint64_t p, uint64_t len, uint64_t tile
 // locally partitioned keys, if the local pass already ran: still the same buckets).
 // The context's side stream and its two events (created on first use).
 static int side_stream(dsort_ctx *ctx) {
-    if (!ctx->side && hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking) != hipSuccess)
+    if (!ctx->side && hipStreamCreateWithFlags(&ctx->side.h, hipStreamNonBlocking) != hipSuccess)
         return set_err(ctx, DSORT_EHIP, "hipStreamCreate");
-    if (!ctx->side_ev && hipEventCreateWithFlags(&ctx->side_ev, hipEventDisableTiming) != hipSuccess)
+    if (!ctx->side_ev && hipEventCreateWithFlags(&ctx->side_ev.h, hipEventDisableTiming) != hipSuccess)
         return set_err(ctx, DSORT_EHIP, "hipEventCreate");
-    if (!ctx->ready_ev && hipEventCreateWithFlags(&ctx->ready_ev, hipEventDisableTiming) != hipSuccess)
+    if (!ctx->ready_ev && hipEventCreateWithFlags(&ctx->ready_ev.h, hipEventDisableTiming) != hipSuccess)
         return set_err(ctx, DSORT_EHIP, "hipEventCreate");
     return DSORT_OK;
 }
@@ -1792,8 +1767,8 @@ static int merge_split_subbuckets(dsort_ctx *ctx, const sb::Ovf *d_ovf, uint32_t
     // exchange's later waves), then back
     uint64_t mx = 0;
     for (const Ovf &o : ov) mx = o.len > mx ? o.len : mx;
-    if (int rc_ = ensure(ctx, &ctx->stmp, &ctx->stmp_bytes, mx * sizeof(T) + 16, "split sub-bucket merge")) return rc_;
-    T *tmp = static_cast<T *>(ctx->stmp);
+    if (int rc_ = ensure(ctx, ctx->stmp, mx * sizeof(T) + 16, "split sub-bucket merge")) return rc_;
+    T *tmp = ctx->stmp.as<T>();
     int lv = 0;
     for (const Ovf &o : ov) {
         std::vector<GTile> gt(o.nt);
@@ -2081,25 +2056,23 @@ static int sub_stage(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T> &p, S
     const uint64_t CH = p.CH, nch = p.nch;
     const PieceMap<T> *pm = a.pm;
     const std::vector<BInfo> &bi = p.bi;
-    int rc = ensure(ctx, &ctx->sub, &ctx->sub_bytes, p.arena_bytes, "sub-bucket partition");
+    int rc = ensure(ctx, ctx->sub, p.arena_bytes, "sub-bucket partition");
     if (rc) return rc;
-    sub_arena<T>(a, p, reinterpret_cast<uintptr_t>(ctx->sub), A);
+    sub_arena<T>(a, p, reinterpret_cast<uintptr_t>(ctx->sub.p), A);
     // pinned staging: the two tables, the sample tiles + count, then the two counters read back
     const size_t h_ch = (B * sizeof(BInfo) + 15) & ~(size_t)15, h_stl = h_ch + nch * sizeof(Chunk);
     const size_t h_num = h_stl + B * sizeof(bk::TileRef) + 16;
     const size_t h_fill = h_num + 16;
     const size_t hbytes = h_fill + (pm || a.fill_keys ? B * sizeof(FillSeg<T>) : 0);
-    if (!ctx->sub_ev && hipEventCreateWithFlags(&ctx->sub_ev, hipEventDisableTiming) != hipSuccess)
+    if (!ctx->sub_ev && hipEventCreateWithFlags(&ctx->sub_ev.h, hipEventDisableTiming) != hipSuccess)
         return set_err(ctx, DSORT_EHIP, "hipEventCreate");
     if (int rc_ = sync_event(ctx, ctx->sub_ev, "tile count")) return rc_;  // the previous call's read-back is done with the staging
-    if (ctx->sub_host_bytes < hbytes) {  // (after that wait: the previous call's uploads are done with it)
+    if (ctx->sub_host.bytes < hbytes) {  // (after that wait: the previous call's uploads are done with it)
         release_host(ctx, ctx->sub_host);
-        ctx->sub_host = nullptr;
-        ctx->sub_host_bytes = 0;
-        DSORT_HIP(ctx, hipHostMalloc(&ctx->sub_host, hbytes, hipHostMallocDefault));
-        ctx->sub_host_bytes = hbytes;
+        DSORT_HIP(ctx, hipHostMalloc(&ctx->sub_host.p, hbytes, hipHostMallocDefault));
+        ctx->sub_host.bytes = hbytes;
     }
-    char *h = static_cast<char *>(ctx->sub_host);
+    char *h = ctx->sub_host.as<char>();
     A.hn = reinterpret_cast<uint32_t *>(h + h_num);
     std::memcpy(h, bi.data(), B * sizeof(BInfo));
     Chunk *hc = reinterpret_cast<Chunk *>(h + h_ch);
@@ -2213,11 +2186,11 @@ static int sub_local_path(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T> 
     int rc;
     // 2. every chunk partitioned in place (cnt = the prefix tables), sub-bucket starts, tiles
     if (p.nch) {
-        if ((rc = stage_event(ctx, s, timed, 13))) return rc;
+        if ((rc = stage_event(ctx, s, timed, wave_ev(ctx, kEvSub0)))) return rc;
         hipLaunchKernelGGL(sb_local_kernel<T>, dim3((unsigned)p.nch), dim3(SB_LT<T>), 0, s, src, A.ch, A.bi, SS, A.spl,
                            A.rng, A.sfn, A.cnt, ctx->bk_hot, A.stot);
         DSORT_HIP(ctx, hipGetLastError());
-        if ((rc = stage_event(ctx, s, timed, 14))) return rc;
+        if ((rc = stage_event(ctx, s, timed, wave_ev(ctx, kEvSub1)))) return rc;
     }
     // (the piece tables inside the scan with many buckets; with few, a kernel of their own)
     constexpr int PIECES_SCAN_MINB = 256;
@@ -2294,7 +2267,7 @@ static int sub_local_path(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T> 
         rc = tile_sort<T, true>(ctx, src, d_keys, n, nullptr, num, ga, ntiles, s, timed, TILE);
         if (rc) return rc;
     }
-    if ((rc = stage_event(ctx, s, timed, 1))) return rc;
+    if ((rc = stage_event(ctx, s, timed, wave_ev(ctx, kEvTileSortDone)))) return rc;
     fault_point(ctx, s, 2);  // tile sort done (a split sub-bucket's merge follows)
     // sub-buckets above a tile (a sampling outlier): their split tiles' outputs merged (src,
     // read by the tile sort, is free scratch now)
@@ -2321,7 +2294,7 @@ static int sub_scatter_path(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T
     int rc;
     // 2. histograms, sub-bucket starts, tiles
     if (nch) {
-        if ((rc = stage_event(ctx, s, timed, 13))) return rc;
+        if ((rc = stage_event(ctx, s, timed, wave_ev(ctx, kEvSub0)))) return rc;
         hipLaunchKernelGGL(sb_hist_kernel<T>, dim3((unsigned)nch), dim3(SB_T), 0, s, src, A.ch, A.bi, SS, A.spl, A.rng,
                            A.sfn, A.cnt);
         DSORT_HIP(ctx, hipGetLastError());
@@ -2336,7 +2309,7 @@ static int sub_scatter_path(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T
         hipLaunchKernelGGL(sb_scatter_kernel<T>, dim3((unsigned)nch), dim3(SB_T), 0, s, src, d_keys, A.ch,
                            (uint32_t)nch, A.bi, SS, A.spl, A.rng, A.sfn, A.offs);
         DSORT_HIP(ctx, hipGetLastError());
-        if ((rc = stage_event(ctx, s, timed, 14))) return rc;
+        if ((rc = stage_event(ctx, s, timed, wave_ev(ctx, kEvSub1)))) return rc;
     }
     if (int rc_ = sync_event(ctx, ctx->sub_ev, "tile count")) return rc_;
     const uint32_t ntiles = A.hn[0], novf = A.hn[1];
@@ -2348,10 +2321,7 @@ static int sub_scatter_path(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T
                                  timed, TILE);
         if (rc) return rc;
     }
-    if (timed && ctx->ev_ok) {
-        DSORT_HIP(ctx, hipEventRecord(ctx->ev[1], s));
-        ctx->ev_mask |= 2u;
-    }
+    if ((rc = stage_event(ctx, s, timed, kEvTileSortDone))) return rc;
     fault_point(ctx, s, 2);  // tile sort done (the oversized sub-buckets' merges follow)
     // 4. oversized sub-buckets: their tile-sorted pieces merged into a buffer of their own, then
     //    copied back.  (Not into src: in the bucket exchange src is the partition buffer, which
@@ -2363,10 +2333,10 @@ static int sub_scatter_path(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T
         if (int rc_ = sync_stream(ctx, s, "sort stream")) return rc_;
         uint64_t mx = 0;
         for (const Ovf &o : ov) mx = o.len > mx ? o.len : mx;
-        if (int rc_ = ensure(ctx, &ctx->stmp, &ctx->stmp_bytes, mx * sizeof(T) + 16, "oversized sub-bucket merge"))
+        if (int rc_ = ensure(ctx, ctx->stmp, mx * sizeof(T) + 16, "oversized sub-bucket merge"))
             return rc_;
         // (the merge output keeps the sub-bucket's misalignment inside a 16-byte chunk)
-        T *tmp = static_cast<T *>(ctx->stmp);
+        T *tmp = ctx->stmp.as<T>();
         int lv = 0;
         for (const Ovf &o : ov) {
             const std::vector<size_t> runs = sub_tile_runs(o.start, o.len, TILE, ALIGN, mis);
@@ -2447,9 +2417,9 @@ static int bk_layout(dsort_ctx *ctx, uint64_t n, int B, size_t smp_bytes, BkLayo
                  o_part = take((size_t)L.nchunk * B * 8 + (size_t)BK_MAXB * 8), o_offs = take((size_t)L.G * B * 4),
                  o_bst = take((size_t)(B + 1) * 8), o_cst = take((size_t)(B + 1) * 8), o_tt = take((size_t)L.tmax * sizeof(TileRef)), o_nt = take(4),
                  o_map = take(BK_MAP_BYTES), o_ids = take(BkIds<T>::ON ? (size_t)L.G * L.subs * BK_T * Geo<T>::KPT * 4 / BkIds<T>::PER_WORD : 0);
-    int rc = ensure(ctx, &ctx->bucket, &ctx->bucket_bytes, off, "bucket partition");
+    int rc = ensure(ctx, ctx->bucket, off, "bucket partition");
     if (rc) return rc;
-    char *a = static_cast<char *>(ctx->bucket);
+    char *a = ctx->bucket.as<char>();
     L.smp = a + o_smp;
     L.spl = reinterpret_cast<C *>(a + o_spl);
     L.cnt = reinterpret_cast<uint32_t *>(a + o_cnt);
@@ -2463,14 +2433,12 @@ static int bk_layout(dsort_ctx *ctx, uint64_t n, int B, size_t smp_bytes, BkLayo
     L.ids = BkIds<T>::ON ? reinterpret_cast<uint32_t *>(a + o_ids) : nullptr;
     // starts, then the splitters, then the slot map (int32 reads its choice back)
     const size_t hbytes = (size_t)(BK_MAXB + 1) * 8 + (size_t)BK_MAXB * 16 + sizeof(BkMap);
-    if (ctx->bucket_host_bytes < hbytes) {
+    if (ctx->bucket_host.bytes < hbytes) {
         release_host(ctx, ctx->bucket_host);
-        ctx->bucket_host = nullptr;
-        ctx->bucket_host_bytes = 0;
-        DSORT_HIP(ctx, hipHostMalloc(&ctx->bucket_host, hbytes, hipHostMallocDefault));
-        ctx->bucket_host_bytes = hbytes;
+        DSORT_HIP(ctx, hipHostMalloc(&ctx->bucket_host.p, hbytes, hipHostMallocDefault));
+        ctx->bucket_host.bytes = hbytes;
     }
-    if (!ctx->bucket_ev && hipEventCreateWithFlags(&ctx->bucket_ev, hipEventDisableTiming) != hipSuccess)
+    if (!ctx->bucket_ev && hipEventCreateWithFlags(&ctx->bucket_ev.h, hipEventDisableTiming) != hipSuccess)
         return set_err(ctx, DSORT_EHIP, "hipEventCreate");
     return DSORT_OK;
 }
@@ -2489,7 +2457,7 @@ static int first_level(dsort_ctx *ctx, const T *d_in, uint64_t n, uint64_t ioff,
     using C = typename Comp<T>::C;
     const int B = L.B, BP = L.BP;
     int rc;
-    hb = static_cast<uint64_t *>(ctx->bucket_host);
+    hb = ctx->bucket_host.as<uint64_t>();
     hspl = reinterpret_cast<C *>(hb + BK_MAXB + 1);
     hipLaunchKernelGGL(bucket_slotmap_kernel<T>, dim3(1), dim3(BK_MAXB), 0, s, L.spl, B, n, L.map);
     ctx->bk_hot = &L.map->hot;
@@ -2502,7 +2470,7 @@ static int first_level(dsort_ctx *ctx, const T *d_in, uint64_t n, uint64_t ioff,
     BkMap *hm = reinterpret_cast<BkMap *>(reinterpret_cast<char *>(hb) + (size_t)(BK_MAXB + 1) * 8 + (size_t)BK_MAXB * 16);
     DSORT_HIP(ctx, hipMemcpyAsync(hm, L.map, sizeof(BkMap), hipMemcpyDeviceToHost, s));
     DSORT_HIP(ctx, hipEventRecord(ctx->bucket_ev, s));
-    if ((rc = stage_event(ctx, s, timed, 9))) return rc;
+    if ((rc = stage_event(ctx, s, timed, kEvHist0))) return rc;
     // (int32: the fixed map's histogram goes first -- it returns at once when the map is adaptive
     // -- so the GPU is busy while the host reads the map's choice; only the adaptive case launches
     // a second instance behind it)
@@ -2515,7 +2483,7 @@ static int first_level(dsort_ctx *ctx, const T *d_in, uint64_t n, uint64_t ioff,
             hipLaunchKernelGGL((bucket_hist_kernel<T, true>), dim3((unsigned)L.G), dim3(BK_T), 0, s, d_in, n, L.spl,
                                L.map, B, BP, L.subs, L.cnt, ioff, L.ids);
     }
-    if ((rc = stage_event(ctx, s, timed, 10))) return rc;
+    if ((rc = stage_event(ctx, s, timed, kEvHist1))) return rc;
     hipLaunchKernelGGL(bucket_colsum_kernel, dim3((unsigned)L.nchunk), dim3(BK_MAXB), 0, s, L.cnt, (uint32_t)L.G, B,
                        L.part);
     // (the column totals after the chunk sums: part's slack)
@@ -2537,7 +2505,7 @@ static int first_level(dsort_ctx *ctx, const T *d_in, uint64_t n, uint64_t ioff,
     DSORT_HIP(ctx, hipMemcpyAsync(hb, L.bst, (size_t)(B + 1) * 8, hipMemcpyDeviceToHost, ctx->side));
     if (B > 1) DSORT_HIP(ctx, hipMemcpyAsync(hspl, L.spl, (size_t)(B - 1) * sizeof(C), hipMemcpyDeviceToHost, ctx->side));
     DSORT_HIP(ctx, hipEventRecord(ctx->bucket_ev, ctx->side));
-    if ((rc = stage_event(ctx, s, timed, 11))) return rc;
+    if ((rc = stage_event(ctx, s, timed, kEvScatter0))) return rc;
     if constexpr (!Comp<T>::ADAPT) {
         if (ad)
             hipLaunchKernelGGL((bucket_scatter_lines_kernel<T, false, true>), dim3((unsigned)L.G), dim3(BK_T), 0, s,
@@ -2556,7 +2524,7 @@ static int first_level(dsort_ctx *ctx, const T *d_in, uint64_t n, uint64_t ioff,
             hipLaunchKernelGGL((bucket_scatter_lines_kernel<T, true>), dim3((unsigned)L.G), dim3(BK_T), 0, s, d_in, n,
                                L.spl, L.map, B, BP, L.subs, L.offs, part_out, direct, ioff, L.ids);
     DSORT_HIP(ctx, hipGetLastError());
-    if ((rc = stage_event(ctx, s, timed, 12))) return rc;
+    if ((rc = stage_event(ctx, s, timed, kEvScatter1))) return rc;
     fault_point(ctx, s, 0);  // first-level partition done
     if (int rc_ = sync_event(ctx, ctx->bucket_ev, "bucket starts")) return rc_;
     if (hb[B] != n) return set_err(ctx, DSORT_EHIP, "bucket partition lost keys");
@@ -2574,7 +2542,7 @@ static int bucketed_stats_start(dsort_ctx *ctx, uint64_t n, int tile, hipStream_
     ctx->ev_mask = 0;
     ctx->kev_used = 0;
     ctx->last_stream = s;
-    return stage_event(ctx, s, timed, 0);
+    return stage_event(ctx, s, timed, kEvStart);
 }
 
 template <typename T>
@@ -2596,9 +2564,9 @@ static int bucket_sort(dsort_ctx *ctx, const T *d_in, T *d_keys, size_t n, hipSt
     uint32_t *ntl = L.ntl;
     const uint64_t tmax = L.tmax;
     // (+ 16 bytes: the gathering tile sort reads the 16-byte vector that holds the last key)
-    rc = ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, n * sizeof(T) + 16, "sort scratch");
+    rc = ensure(ctx, ctx->scratch, n * sizeof(T) + 16, "sort scratch");
     if (rc) return rc;
-    T *scratch = static_cast<T *>(ctx->scratch);
+    T *scratch = ctx->scratch.as<T>();
     // 1. splitters from a regular sample in (key, input index) order, sorted on the GPU (the
     // sample sorts never bucket and never fire the fault injection)
     int64_t *pk = reinterpret_cast<int64_t *>(smp), *psrt = pk + S, *pcmp = pk + 2 * (size_t)S;
@@ -2677,10 +2645,7 @@ static int bucket_sort(dsort_ctx *ctx, const T *d_in, T *d_keys, size_t n, hipSt
     rc = tile_sort<T, false>(ctx, part_out, bufs[cur], n, reinterpret_cast<const uint4 *>(tt), ntl, sb::Gather{},
                              (uint32_t)tmax, s, timed);
     if (rc) return rc;
-    if (timed && ctx->ev_ok) {
-        DSORT_HIP(ctx, hipEventRecord(ctx->ev[1], s));
-        ctx->ev_mask |= 2u;
-    }
+    if ((rc = stage_event(ctx, s, timed, kEvTileSortDone))) return rc;
     fault_point(ctx, s, 1);  // tile sort done
     // 4. group tables of every pass (one staging buffer, one copy).  Every bucket gets its own
     // fan-in per pass: the passes after the first keep the global plan's fan-in and the first
@@ -2758,24 +2723,22 @@ static int bucket_sort(dsort_ctx *ctx, const T *d_in, T *d_keys, size_t n, hipSt
         const size_t tb_off = (gbytes + 255) & ~(size_t)255;
         if (ctx->groups_ev_pending) { if (int rc_ = sync_event(ctx, ctx->groups_ev, "group table")) return rc_; }
         ctx->groups_ev_pending = false;
-        if (ctx->groups_host_bytes < tb_off + tbytes) {
+        if (ctx->groups_host.bytes < tb_off + tbytes) {
             release_host(ctx, ctx->groups_host);
-            ctx->groups_host = nullptr;
-            ctx->groups_host_bytes = 0;
-            DSORT_HIP(ctx, hipHostMalloc(&ctx->groups_host, tb_off + tbytes, hipHostMallocDefault));
-            ctx->groups_host_bytes = tb_off + tbytes;
+            DSORT_HIP(ctx, hipHostMalloc(&ctx->groups_host.p, tb_off + tbytes, hipHostMallocDefault));
+            ctx->groups_host.bytes = tb_off + tbytes;
         }
-        rc = ensure(ctx, &ctx->groups, &ctx->groups_bytes, tb_off + tbytes, "group table");
+        rc = ensure(ctx, ctx->groups, tb_off + tbytes, "group table");
         if (rc) return rc;
-        std::memcpy(ctx->groups_host, groups.data(), gbytes);
-        std::memcpy(static_cast<char *>(ctx->groups_host) + tb_off, tgroup.data(), tbytes);
-        DSORT_HIP(ctx, hipMemcpyAsync(ctx->groups, ctx->groups_host, tb_off + tbytes, hipMemcpyHostToDevice, s));
-        if (!ctx->groups_ev && hipEventCreateWithFlags(&ctx->groups_ev, hipEventDisableTiming) != hipSuccess)
+        std::memcpy(ctx->groups_host.p, groups.data(), gbytes);
+        std::memcpy(ctx->groups_host.as<char>() + tb_off, tgroup.data(), tbytes);
+        DSORT_HIP(ctx, hipMemcpyAsync(ctx->groups.p, ctx->groups_host.p, tb_off + tbytes, hipMemcpyHostToDevice, s));
+        if (!ctx->groups_ev && hipEventCreateWithFlags(&ctx->groups_ev.h, hipEventDisableTiming) != hipSuccess)
             return set_err(ctx, DSORT_EHIP, "hipEventCreate");
         DSORT_HIP(ctx, hipEventRecord(ctx->groups_ev, s));
         ctx->groups_ev_pending = true;
-        const GroupK *dg = static_cast<const GroupK *>(ctx->groups);
-        const uint32_t *dt = reinterpret_cast<const uint32_t *>(static_cast<const char *>(ctx->groups) + tb_off);
+        const GroupK *dg = ctx->groups.as<const GroupK>();
+        const uint32_t *dt = reinterpret_cast<const uint32_t *>(ctx->groups.as<const char>() + tb_off);
         for (size_t q = 0; q < plan.size(); ++q) {
             PassDesc pd{(uint64_t)n, 0, 1 << plan[q].logf, (int)plan[q].ngroups, dg + plan[q].group_off};
             pd.tile_group = dt + plan[q].tile_off;
@@ -2787,11 +2750,7 @@ static int bucket_sort(dsort_ctx *ctx, const T *d_in, T *d_keys, size_t n, hipSt
             }
         }
     }
-    if (timed && ctx->ev_ok) {
-        DSORT_HIP(ctx, hipEventRecord(ctx->ev[2], s));
-        ctx->ev_mask |= 4u;
-    }
-    return DSORT_OK;
+    return stage_event(ctx, s, timed, kEvLocalDone);
 }
 
 // ---- bucket exchange (dsort_internal.h; the multi-GPU sample sort) ------------
@@ -2854,6 +2813,28 @@ static int bx_layout(dsort_ctx *ctx, const BxPlan &pl, BkLayout<T> &L) {
 }
 
 }  // namespace wv
+
+// Every stage boundary of the outermost timed sort also opens / closes a roctx range on the host
+// thread (rocprofv3 --marker-trace shows when each stage was enqueued; the device times are the
+// events'): dsort:histogram, dsort:scatter, dsort:second-level, dsort:tile-sort.
+static void stage_range(const dsort_ctx *ctx, StageEv e) {
+    if (ctx->nested) return;
+    switch (e >= kWave0Offset ? e - kWave0Offset : e) {
+        case kEvHist0: roctxRangePushA("dsort:histogram"); break;
+        case kEvScatter0: roctxRangePushA("dsort:scatter"); break;
+        case kEvSub0: roctxRangePushA("dsort:second-level"); break;
+        case kEvTile0: roctxRangePushA("dsort:tile-sort"); break;
+        case kEvHist1: case kEvScatter1: case kEvSub1: case kEvTile1: roctxRangePop(); break;
+        default: break;
+    }
+}
+int stage_event(dsort_ctx *ctx, hipStream_t s, bool timed, StageEv e) {
+    if (timed) stage_range(ctx, e);
+    if (!timed || !ctx->ev_ok) return DSORT_OK;
+    DSORT_HIP(ctx, hipEventRecord(ctx->ev[e], s));
+    ctx->ev_mask |= 1u << e;
+    return DSORT_OK;
+}
 
 bool bx_make_plan(const dsort_opts &opt, int P, int me, const uint64_t *n_of, int key_bytes, BxPlan &pl) {
     pl.P = P;
@@ -2936,9 +2917,9 @@ int bx_partition(dsort_ctx *ctx, const T *d_in, const BxPlan &pl, const BxSample
     hipLaunchKernelGGL(bx_splitter_kernel<T>, dim3(1), dim3(bk::BK_MAXB), 0, s, sizeof(T) == 4 ? psrt : pcmp, pk, d_all,
                        S_real, pl.Btot, L.BP, L.spl);
     DSORT_HIP(ctx, hipGetLastError());
-    rc = ensure(ctx, &ctx->scratch, &ctx->scratch_bytes, (pl.n_local + pl.recv_room) * sizeof(T) + 16, "sort scratch");
+    rc = ensure(ctx, ctx->scratch, (pl.n_local + pl.recv_room) * sizeof(T) + 16, "sort scratch");
     if (rc) return rc;
-    T *scratch = static_cast<T *>(ctx->scratch);
+    T *scratch = ctx->scratch.as<T>();
     uint64_t *hb;
     C *hspl;
     if (pl.n_local) {
@@ -2947,14 +2928,14 @@ int bx_partition(dsort_ctx *ctx, const T *d_in, const BxPlan &pl, const BxSample
         if (rc) return rc;
     } else {
         // no keys here: empty buckets (the splitters still go to the host for the second level)
-        hb = static_cast<uint64_t *>(ctx->bucket_host);
+        hb = ctx->bucket_host.as<uint64_t>();
         hspl = reinterpret_cast<C *>(hb + bk::BK_MAXB + 1);
         for (int b = 0; b <= pl.Btot; ++b) hb[b] = 0;
         DSORT_HIP(ctx, hipMemcpyAsync(hspl, L.spl, (size_t)(pl.Btot - 1) * sizeof(C), hipMemcpyDeviceToHost, s));
         if (int rc_ = sync_stream(ctx, s, "sort stream")) return rc_;
         fault_point(ctx, s, 0);
     }
-    if ((rc = stage_event(ctx, s, timed, 2))) return rc;  // the local part done: the exchange starts
+    if ((rc = stage_event(ctx, s, timed, kEvLocalDone))) return rc;  // the local part done: the exchange starts
     // (the scatter's rule, bucket_scatter_lines_kernel / bucket_scan_kernel: the same splitters on
     // every rank, which derive every rank's compacted starts from its bucket starts)
     pure.assign((size_t)pl.Btot, 0);
@@ -2979,7 +2960,7 @@ int bx_local_sort(dsort_ctx *ctx, T *recv, T *out, const BxPlan &pl, const uint6
     pm.pure_key.assign(Bl, T(0));
     std::vector<uint64_t> hbo(Bl + 1, 0);
     std::vector<uint8_t> pure(Bl, 0);
-    const C *hspl = reinterpret_cast<const C *>(static_cast<const uint64_t *>(ctx->bucket_host) + bk::BK_MAXB + 1);
+    const C *hspl = reinterpret_cast<const C *>(ctx->bucket_host.as<const uint64_t>() + bk::BK_MAXB + 1);
     for (int j = 0; j < Bl; ++j) {
         const uint64_t g = g0 + (uint64_t)j;
         pm.first[j] = (uint32_t)pm.p.size();
@@ -3011,19 +2992,17 @@ int bx_local_sort(dsort_ctx *ctx, T *recv, T *out, const BxPlan &pl, const uint6
         // a second wave's tables go to the other second-level arena: the first wave's kernels may
         // still read theirs when this wave's tables are uploaded
         if (w & 1) {
-            std::swap(ctx->sub, ctx->sub_alt);
-            std::swap(ctx->sub_bytes, ctx->sub_alt_bytes);
+            ctx->sub.swap(ctx->sub_alt);
         }
         const int saved_done = ctx->ev_done, saved_off = ctx->ev_off;
-        ctx->ev_off = last ? 0 : 15;
-        ctx->ev_done = last ? 4 : 16;
+        ctx->ev_off = last ? 0 : kWave0Offset;
+        ctx->ev_done = last ? kEvFinalDone : kEvWave0Done;
         rc = sub_sort<T>(ctx, recv, out + out_off, nrecv, hbo.data(), Bl, sub_keys<T>(ctx), s, timed,
                          ctx->opt.sub_gather != 0, pure.data(), false, L.spl + g0, &pm);
         ctx->ev_done = saved_done;
         ctx->ev_off = saved_off;
         if (w & 1) {
-            std::swap(ctx->sub, ctx->sub_alt);
-            std::swap(ctx->sub_bytes, ctx->sub_alt_bytes);
+            ctx->sub.swap(ctx->sub_alt);
         }
         if (rc) return rc;
         if (w > 0) {
@@ -3037,10 +3016,7 @@ int bx_local_sort(dsort_ctx *ctx, T *recv, T *out, const BxPlan &pl, const uint6
             fault_point(ctx, s, 1);
             fault_point(ctx, s, 2);
         }
-        if (last && timed && ctx->ev_ok) {
-            DSORT_HIP(ctx, hipEventRecord(ctx->ev[4], s));
-            ctx->ev_mask |= 16u;
-        }
+        if (last && (rc = stage_event(ctx, s, timed, kEvFinalDone))) return rc;
     }
     if (!last) return DSORT_OK;
     if (ctx->opt.kill_after_pass >= 0)  // (a kill stage this sort never reached)
@@ -3088,26 +3064,20 @@ static int wave_sort(dsort_ctx *ctx, const T *d_in, T *d_keys, size_t n, hipStre
     T *scratch = nullptr;
     if (passes > 0) {
         // a nested sort (splitter samples) runs while the scratch holds the partitioned keys
-        void **sb = ctx->nested ? &ctx->scratch2 : &ctx->scratch;
-        size_t *sbb = ctx->nested ? &ctx->scratch2_bytes : &ctx->scratch_bytes;
-        int rc = ensure(ctx, sb, sbb, n * sizeof(T), "sort scratch");
+        DevBuf &sb = ctx->nested ? ctx->scratch2 : ctx->scratch;
+        int rc = ensure(ctx, sb, n * sizeof(T), "sort scratch");
         if (rc) return rc;
-        scratch = static_cast<T *>(*sb);
+        scratch = sb.as<T>();
     }
     // ping-pong so that the last pass lands in d_keys; the tile sort reads d_in (which may alias
     // d_keys)
     T *bufs[2] = {d_keys, scratch};
     int cur = (passes % 2 == 0) ? 0 : 1;
-    if (timed && ctx->ev_ok) {
-        DSORT_HIP(ctx, hipEventRecord(ctx->ev[0], s));
-        ctx->ev_mask |= 1u;
-    }
-    int rc = tile_sort<T, false>(ctx, d_in, bufs[cur], n, nullptr, nullptr, sb::Gather{}, (uint32_t)tiles, s, timed);
+    int rc = stage_event(ctx, s, timed, kEvStart);
     if (rc) return rc;
-    if (timed && ctx->ev_ok) {
-        DSORT_HIP(ctx, hipEventRecord(ctx->ev[1], s));
-        ctx->ev_mask |= 2u;
-    }
+    rc = tile_sort<T, false>(ctx, d_in, bufs[cur], n, nullptr, nullptr, sb::Gather{}, (uint32_t)tiles, s, timed);
+    if (rc) return rc;
+    if ((rc = stage_event(ctx, s, timed, kEvTileSortDone))) return rc;
     fault_point(ctx, s, 0);  // tile sort done
     constexpr uint64_t MTN = MTNOM_OF<T>;
     uint64_t Rr = TILE;
@@ -3123,11 +3093,7 @@ static int wave_sort(dsort_ctx *ctx, const T *d_in, T *d_keys, size_t n, hipStre
         cur ^= 1;
         fault_point(ctx, s, 1 + p);  // merge pass p done
     }
-    if (timed && ctx->ev_ok) {
-        DSORT_HIP(ctx, hipEventRecord(ctx->ev[2], s));
-        ctx->ev_mask |= 4u;
-    }
-    return DSORT_OK;
+    return stage_event(ctx, s, timed, kEvLocalDone);
 }
 
 // k-way merge of back-to-back runs of arbitrary lengths (the master merge, server.c:481-515, and
@@ -3160,13 +3126,13 @@ static int wave_merge(dsort_ctx *ctx, const T *d_in, const size_t *lens, int k, 
     if (!keep_stats) ctx->stats.merge_passes = levels;
     int rc;
     if (levels > 1) {
-        rc = ensure(ctx, &ctx->scratch2, &ctx->scratch2_bytes, n * sizeof(T), "merge scratch");
+        rc = ensure(ctx, ctx->scratch2, n * sizeof(T), "merge scratch");
         if (rc) return rc;
     }
-    T *dsts[2] = {d_out, static_cast<T *>(ctx->scratch2)};
+    T *dsts[2] = {d_out, ctx->scratch2.as<T>()};
     int which = (levels % 2 == 1) ? 0 : 1;
     const T *src = d_in;
-    if (!ctx->groups_ev && hipEventCreateWithFlags(&ctx->groups_ev, hipEventDisableTiming) != hipSuccess)
+    if (!ctx->groups_ev && hipEventCreateWithFlags(&ctx->groups_ev.h, hipEventDisableTiming) != hipSuccess)
         return set_err(ctx, DSORT_EHIP, "hipEventCreate");
     constexpr uint64_t MTN = MTNOM_OF<T>;
     for (int l = 0; l < levels; ++l) {
@@ -3177,16 +3143,14 @@ static int wave_merge(dsort_ctx *ctx, const T *d_in, const size_t *lens, int k, 
         const size_t gbytes = (size_t)ng * sizeof(GroupK);
         if (ctx->groups_ev_pending) { if (int rc_ = sync_event(ctx, ctx->groups_ev, "group table")) return rc_; }
         ctx->groups_ev_pending = false;
-        if (ctx->groups_host_bytes < gbytes) {
+        if (ctx->groups_host.bytes < gbytes) {
             release_host(ctx, ctx->groups_host);
-            ctx->groups_host = nullptr;
-            ctx->groups_host_bytes = 0;
-            DSORT_HIP(ctx, hipHostMalloc(&ctx->groups_host, gbytes, hipHostMallocDefault));
-            ctx->groups_host_bytes = gbytes;
+            DSORT_HIP(ctx, hipHostMalloc(&ctx->groups_host.p, gbytes, hipHostMallocDefault));
+            ctx->groups_host.bytes = gbytes;
         }
-        rc = ensure(ctx, &ctx->groups, &ctx->groups_bytes, gbytes, "group table");
+        rc = ensure(ctx, ctx->groups, gbytes, "group table");
         if (rc) return rc;
-        GroupK *gh = static_cast<GroupK *>(ctx->groups_host);
+        GroupK *gh = ctx->groups_host.as<GroupK>();
         std::vector<uint64_t> next;
         uint64_t base = 0, tiles = 0;
         for (int gi = 0; gi < ng; ++gi) {
@@ -3207,10 +3171,10 @@ static int wave_merge(dsort_ctx *ctx, const T *d_in, const size_t *lens, int k, 
             base += tot;
             next.push_back(tot);
         }
-        DSORT_HIP(ctx, hipMemcpyAsync(ctx->groups, gh, gbytes, hipMemcpyHostToDevice, s));
+        DSORT_HIP(ctx, hipMemcpyAsync(ctx->groups.p, gh, gbytes, hipMemcpyHostToDevice, s));
         DSORT_HIP(ctx, hipEventRecord(ctx->groups_ev, s));
         ctx->groups_ev_pending = true;
-        PassDesc pd{n, 0, 1 << logf, ng, static_cast<const GroupK *>(ctx->groups)};
+        PassDesc pd{n, 0, 1 << logf, ng, ctx->groups.as<const GroupK>()};
         T *dst = dsts[which];
         // a top-level merge times its merge kernels (dsort_stats.merge_kernel_ms)
         rc = launch_pass_w<T, false>(ctx, src, dst, pd, logf, tiles, s, !keep_stats);
@@ -3310,7 +3274,7 @@ int order_begin(dsort_ctx *ctx, hipStream_t s) {
 }
 int order_end(dsort_ctx *ctx, hipStream_t s) {
     if (ctx->nested) return DSORT_OK;
-    if (!ctx->done_ev && hipEventCreateWithFlags(&ctx->done_ev, hipEventDisableTiming) != hipSuccess)
+    if (!ctx->done_ev && hipEventCreateWithFlags(&ctx->done_ev.h, hipEventDisableTiming) != hipSuccess)
         return set_err(ctx, DSORT_EHIP, "hipEventCreate");
     DSORT_HIP(ctx, hipEventRecord(ctx->done_ev, s));
     ctx->done_stream = s;
