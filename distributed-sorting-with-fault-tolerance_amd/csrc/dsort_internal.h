@@ -158,6 +158,9 @@ struct dsort_opts {
     int64_t argsort_wide = 0;       // DSORT_OPT_ARGSORT_WIDE
     int64_t test_fail_leg = -1;     // DSORT_OPT_TEST_FAIL_LEG
     int64_t topk_path = -1;         // DSORT_OPT_TOPK_PATH: -1 dsort_plan_topk's rule, 0 full argsort, 1 select
+    int64_t sub_arith = -1;         // not an ABI option (dsort_debug_sub_arith_mode): the second level's arithmetic
+                                    // sub-bucket map: -1 per bucket by the sample rule, 0 off, 2 (tests) every
+                                    // bucket whose span allows it
 };
 
 // The context.  One per host thread, bound to one device.
@@ -281,6 +284,8 @@ struct dsort_ctx {
     HostBuf small_host;  // pinned
     DevBuf bxs;    // bucket exchange: this rank's and every rank's splitter samples
     const uint32_t *bk_hot = nullptr;  // the last first level's runs flag (device, BkMap.hot)
+    uint32_t sub_arith_n[2] = {0, 0};  // the last bucketed sort: buckets of several sub-buckets, and those of
+                                       // them on the arithmetic map (dsort_debug_sub_arith)
     int ev_off = 0;               // kWave0Offset while the bucket exchange's first wave runs its second
                                   // level and tile sort (dsort_get_stats adds the two waves up)
     int ev_done = dsort::kEvLocalDone;  // the stage event a sort's second level records at its end (the

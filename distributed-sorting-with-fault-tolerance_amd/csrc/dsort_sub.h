@@ -19,7 +19,8 @@
 //   (the samples of all buckets sorted by (key, position) in one nested int64 sort of
 //   composites -- int64 keys first sort the keys and rank them, sb_rank_kernel -- bucket b's
 //   samples keep their range [soff, soff + ns) since the buckets are ordered)
-//   sb_splitter_kernel  per bucket: nsub - 1 splitters (key, position) + the slot table
+//   sb_splitter_kernel  per bucket: nsub - 1 splitters (key, position) + the slot table -- sampled, or (int32,
+//                       keys spread evenly over the bucket's range) those of the arithmetic map arith_sub
 //   sb_hist_kernel      per chunk (<= SB_CH keys of one bucket): keys per sub-bucket
 //   sb_scan_kernel      per bucket: sub-bucket starts, per-chunk offsets, tile packing
 //   sb_scatter_kernel   per chunk: keys grouped by sub-bucket in LDS, written to their places
@@ -93,7 +94,7 @@ template <typename T>
 struct SlotFn {      // slot(key) = (clamp(key, klo, ..) - klo) >> sh, capped at SB_SLOTS - 1
     T klo;
     uint32_t sh;
-    uint32_t pad;
+    uint32_t scale;  // != 0: the bucket's sub-buckets are arith_sub(key, klo, scale, nsub) (below)
 };
 
 template <typename T>
@@ -115,9 +116,60 @@ template <> struct __attribute__((aligned(16))) Spl<int64_t> {
     uint32_t p, pad;
 };
 
+// The arithmetic sub-bucket map (int32).  After the first level a bucket covers
+// about 1/1024 of the key space, and where the keys' density is smooth at that scale the sampled
+// splitters only restate an even division of the bucket's key range [klo, klo + span].  Such a
+// bucket's sub-bucket is a pure function of the key,
+//     arith_sub(key) = min(umulhi(max(key - klo, 0), scale), nsub - 1),
+//     scale = floor(nsub * 2^32 / (span + 1)),
+// monotone in the key: nsub sub-buckets of equal key width over the range, keys below it in
+// sub-bucket 0 and keys above it running on to nsub - 1.  sb_splitter_kernel decides per bucket
+// (SlotFn.scale != 0) and then writes SYNTHETIC splitters, arith_splitter(j) = (the largest key with
+// arith_sub <= j, position UINT32_MAX), and the slot table over them, so sub_of on the tables
+// returns arith_sub(key) for every key at every position below UINT32_MAX: the tile sort's bounds,
+// the histogram and scatter kernels and the retry paths read the tables as before, and only
+// sb_local_kernel takes the short cut.  span >= 2 nsub (arith_span_ok) makes scale < 2^31, hence
+// the splitters' offsets ceil((j + 1) 2^32 / scale) - 1 strictly increasing; only the last of them
+// can pass the bucket's range (scale is rounded down), and only that one can pass INT32_MAX, where it
+// is capped -- no key lies above it then, and no two splitters are equal.
+// int64 keys stay on the sampled path: a 64-bit multiply-high per key was not tried (SB_ARITH).
+template <typename T> constexpr bool SB_ARITH = sizeof(T) == 4;
+__host__ __device__ __forceinline__ bool arith_span_ok(uint32_t span, uint32_t nsub) { return span >= 2 * nsub; }
+__host__ __device__ __forceinline__ uint32_t arith_scale(uint32_t span, uint32_t nsub) {
+    return (uint32_t)(((uint64_t)nsub << 32) / ((uint64_t)span + 1));
+}
+__host__ __device__ __forceinline__ uint32_t arith_sub(int32_t key, int32_t klo, uint32_t scale, uint32_t nsub) {
+    const uint32_t d = key < klo ? 0u : (uint32_t)key - (uint32_t)klo;
+    const uint32_t j = (uint32_t)(((uint64_t)d * scale) >> 32);
+    return j < nsub - 1 ? j : nsub - 1;
+}
+// the key of synthetic splitter j (j < nsub - 1)
+__host__ __device__ __forceinline__ int32_t arith_splitter_key(int32_t klo, uint32_t scale, uint32_t j) {
+    const uint64_t d = ((((uint64_t)j + 1) << 32) + scale - 1) / scale - 1;
+    const int64_t k = (int64_t)klo + (int64_t)d;
+    return k < (int64_t)INT32_MAX ? (int32_t)k : INT32_MAX;
+}
+// The rule a bucket takes the map by, beyond the span: none of its arithmetic sub-buckets holds
+// more than SB_ARITH_MAXS * os of the bucket's nsub * os samples, i.e. is predicted above three
+// nominal sub-buckets (about 4.6 K of a tile's 7.8 K keys of room: 1.7x headroom for the sampling
+// error).  Uniform keys: a sub-bucket's samples are about Poisson(os = 8), P(> 24) ~ 1e-6 each.
+constexpr uint32_t SB_ARITH_MAXS = 3;
+// Clumped samples.  On sorted or reversed input the first level keeps a workgroup's keys together but
+// not in order, and a sample run is SB_RUN adjacent keys of its output, so a bucket's samples are nsub
+// clumps of 8 nearly equal keys, each displaced by up to a workgroup's keys: the counts come in whole
+// runs (measured on sorted uniform keys: 30 % of the arithmetic sub-buckets hold no sample, one in 150
+// holds four runs, none of 2400 five) and say little about one sub-bucket.  The sampled splitters are
+// built from the same clumps and come out far less even than the arithmetic map there.  Such a bucket
+// is known by its samples: in (key, position) order at least half of the neighbours come from one run
+// (sorted input: 7 of 8; shuffled input: about 7 in nsub * os).  It takes the map up to six runs in a
+// sub-bucket: a duplicate run of 12 K copies or more (eight sample runs) is still refused, one of 8-11 K
+// copies may pass and is then split and merged.  (The first level's own runs flag, BkMap.hot, needs 16
+// splitters and is not set in a sort of few buckets.)
+constexpr uint32_t SB_ARITH_MAXS_RUNS = 6;
+
 // splitter s lies below key `key` at position `pos`
 template <typename T>
-__device__ __forceinline__ bool below(const Spl<T> &s, T key, uint32_t pos) {
+__host__ __device__ __forceinline__ bool below(const Spl<T> &s, T key, uint32_t pos) {
     return s.k < key || (s.k == key && s.p <= pos);
 }
 
@@ -137,7 +189,7 @@ __device__ __forceinline__ bool below(const Spl<T> &s, T key, uint32_t pos) {
 // places keys on the local path; the scatter path's two passes both call it.
 constexpr uint32_t SB_ONEKEY = 0x8000u;
 template <typename T>
-__device__ __forceinline__ int sub_pick(const Spl<T> *spl, uint32_t r, const Spl<T> &a, const Spl<T> &b, T key,
+__host__ __device__ __forceinline__ int sub_pick(const Spl<T> *spl, uint32_t r, const Spl<T> &a, const Spl<T> &b, T key,
                                         uint32_t pos) {
     int lo = (int)(r & 0x7FFF);
     const int hi = (int)(r >> 16);
@@ -164,7 +216,7 @@ __device__ __forceinline__ int sub_pick(const Spl<T> *spl, uint32_t r, const Spl
     return lo;
 }
 template <typename T>
-__device__ __forceinline__ int sub_of(const Spl<T> *spl, const uint32_t *rng, T klo, uint32_t sh, T key,
+__host__ __device__ __forceinline__ int sub_of(const Spl<T> *spl, const uint32_t *rng, T klo, uint32_t sh, T key,
                                       uint32_t pos) {
     // the slot's first two splitters, read only by the lanes whose slot holds them (a slot holds
     // none in about 60 % of the keys' cases at 2^30 uniform: fewer lanes in every random LDS read,
@@ -295,12 +347,44 @@ __global__ void __launch_bounds__(SB_T) sb_rank_kernel(const int64_t *__restrict
 // output), so duplicates split over sub-buckets exactly like distinct keys (sizes depend on the
 // sample positions only).  Then the slot table: rng[s] = (splitters with slot < s) |
 // (splitters with slot <= s) << 16.
+// Slot s's entry from the splitters' slots (ascending) and keys.
+template <typename T>
+__host__ __device__ __forceinline__ uint32_t slot_entry(const uint32_t *sslot, const T *skey, uint32_t nspl, uint32_t s) {
+    uint32_t lo = 0, hi = nspl;
+    while (lo < hi) {  // first splitter with slot >= s
+        const uint32_t mid = (lo + hi) >> 1;
+        if (sslot[mid] < s) lo = mid + 1;
+        else hi = mid;
+    }
+    uint32_t lo2 = lo, hi2 = nspl;
+    while (lo2 < hi2) {  // first splitter with slot > s
+        const uint32_t mid = (lo2 + hi2) >> 1;
+        if (sslot[mid] <= s) lo2 = mid + 1;
+        else hi2 = mid;
+    }
+    const bool one = lo2 >= lo + 3 && skey[lo] == skey[lo2 - 1];
+    return lo | (one ? SB_ONEKEY : 0u) | (lo2 << 16);
+}
+// the slot map's shift for a bucket whose samples span `span`
+template <typename T>
+__host__ __device__ __forceinline__ uint32_t slot_shift(typename KeyU<T>::U span) {
+    using U = typename KeyU<T>::U;
+    uint32_t sh = 0;
+    while (sh < 8 * sizeof(T) && (span >> sh) >= (U)SB_SLOTS) ++sh;
+    return sh;
+}
+
+// arith (int32): -1 = a bucket takes the arithmetic map (arith_sub above) when its span allows it
+// and no arithmetic sub-bucket holds more than SB_ARITH_MAXS * os of its samples; 0 = never;
+// 2 (tests) = whenever the span allows it, whatever the samples say.  actr (not null): [0] += 1 per
+// bucket of several sub-buckets, [1] += 1 per bucket that took the map.
 template <typename T>
 __global__ void __launch_bounds__(SB_MAXS) sb_splitter_kernel(const int64_t *__restrict__ cmp, const T *__restrict__ smp,
                                                               const BInfo *__restrict__ bi, const Chunk *__restrict__ ch,
                                                               int os, int SS,
                                                               Spl<T> *__restrict__ spl, uint32_t *__restrict__ rng,
-                                                              SlotFn<T> *__restrict__ sfn, uint32_t *__restrict__ stot) {
+                                                              SlotFn<T> *__restrict__ sfn, uint32_t *__restrict__ stot,
+                                                              int arith, uint32_t *__restrict__ actr) {
     using U = typename KeyU<T>::U;
     __shared__ uint32_t sslot[SB_MAXS];
     __shared__ T skey[SB_MAXS];
@@ -310,41 +394,66 @@ __global__ void __launch_bounds__(SB_MAXS) sb_splitter_kernel(const int64_t *__r
         for (int j = tid; j < SS; j += SB_MAXS) stot[(uint64_t)blockIdx.x * SS + j] = 0;
     const int nspl = (int)b.nsub - 1;
     T klo = 0;
-    uint32_t sh = 0;
+    uint32_t sh = 0, scale = 0;
     if (nspl > 0) {
         const int64_t *cm = cmp + b.soff;
         klo = smp[(uint32_t)cm[0]];
         const U span = (U)((U)smp[(uint32_t)cm[b.ns - 1]] - (U)klo);
-        while (sh < 8 * sizeof(T) && (span >> sh) >= (U)SB_SLOTS) ++sh;
+        sh = slot_shift<T>(span);
+        if constexpr (SB_ARITH<T>) {
+            // (block-uniform: b, arith and the span)
+            constexpr uint32_t MAXNS = SB_MAXS * 8;  // a bucket's samples fit one int64 tile (sub_plan's kMaxOs)
+            __shared__ int32_t sk[MAXNS];  // the samples' keys in order (a composite's high word)
+            __shared__ uint32_t bad, same;
+            if (arith != 0 && b.ns <= MAXNS && arith_span_ok((uint32_t)span, b.nsub)) {
+                scale = arith_scale((uint32_t)span, b.nsub);
+                if (arith < 0) {
+                    for (uint32_t i = tid; i < b.ns; i += SB_MAXS) sk[i] = (int32_t)(cm[i] >> 32);
+                    if (tid == 0) bad = same = 0;
+                    __syncthreads();
+                    // neighbours in (key, position) order from one sample run (SB_ARITH_MAXS_RUNS)
+                    if (const uint32_t run = sample_run(b); run > 1) {
+                        uint32_t n1 = 0;
+                        for (uint32_t i = tid + 1; i < b.ns; i += SB_MAXS)
+                            n1 += ((uint32_t)cm[i] - (uint32_t)b.soff) / run == ((uint32_t)cm[i - 1] - (uint32_t)b.soff) / run;
+                        if (n1) atomicAdd(&same, n1);
+                    }
+                    // samples of sub-bucket tid = those above splitter tid - 1 and not above splitter tid
+                    uint32_t ub = b.ns;
+                    if (tid < nspl) ub = upper_bound_k<int32_t>(sk, b.ns, arith_splitter_key(klo, scale, (uint32_t)tid));
+                    if (tid <= nspl) sslot[tid] = ub;
+                    __syncthreads();
+                    const uint32_t maxs = 2 * same >= b.ns ? SB_ARITH_MAXS_RUNS : SB_ARITH_MAXS;
+                    if (tid <= nspl && ub - (tid ? sslot[tid - 1] : 0u) > maxs * (uint32_t)os) bad = 1;
+                    __syncthreads();
+                    if (bad) scale = 0;
+                    __syncthreads();  // (sslot is rewritten below)
+                }
+            }
+        }
         if (tid < nspl) {
-            const uint32_t g = (uint32_t)cm[(uint32_t)(tid + 1) * (uint32_t)os - 1];
-            const T K = smp[g];
             Spl<T> sp{};
-            sp.k = K;
-            sp.p = (uint32_t)bucket_src_pos(b, ch, sample_pos(b, g - b.soff));
+            if (SB_ARITH<T> && scale) {
+                if constexpr (SB_ARITH<T>) sp.k = arith_splitter_key(klo, scale, (uint32_t)tid);
+                sp.p = UINT32_MAX;
+            } else {
+                const uint32_t g = (uint32_t)cm[(uint32_t)(tid + 1) * (uint32_t)os - 1];
+                sp.k = smp[g];
+                sp.p = (uint32_t)bucket_src_pos(b, ch, sample_pos(b, g - b.soff));
+            }
             spl[(uint64_t)blockIdx.x * SS + tid] = sp;
-            sslot[tid] = slot_of<T>(K, klo, sh);
-            skey[tid] = K;
+            sslot[tid] = slot_of<T>(sp.k, klo, sh);
+            skey[tid] = sp.k;
+        }
+        if (tid == 0 && actr) {
+            atomicAdd(&actr[0], 1u);
+            if (scale) atomicAdd(&actr[1], 1u);
         }
     }
     __syncthreads();
-    for (int s = tid; s < SB_SLOTS; s += SB_MAXS) {
-        uint32_t lo = 0, hi = (uint32_t)(nspl > 0 ? nspl : 0);
-        while (lo < hi) {  // first splitter with slot >= s
-            const uint32_t mid = (lo + hi) >> 1;
-            if (sslot[mid] < (uint32_t)s) lo = mid + 1;
-            else hi = mid;
-        }
-        uint32_t lo2 = lo, hi2 = (uint32_t)(nspl > 0 ? nspl : 0);
-        while (lo2 < hi2) {  // first splitter with slot > s
-            const uint32_t mid = (lo2 + hi2) >> 1;
-            if (sslot[mid] <= (uint32_t)s) lo2 = mid + 1;
-            else hi2 = mid;
-        }
-        const bool one = lo2 >= lo + 3 && skey[lo] == skey[lo2 - 1];
-        rng[(uint64_t)blockIdx.x * SB_SLOTS + s] = lo | (one ? SB_ONEKEY : 0u) | (lo2 << 16);
-    }
-    if (tid == 0) sfn[blockIdx.x] = SlotFn<T>{klo, sh, 0};
+    for (int s = tid; s < SB_SLOTS; s += SB_MAXS)
+        rng[(uint64_t)blockIdx.x * SB_SLOTS + s] = slot_entry<T>(sslot, skey, (uint32_t)(nspl > 0 ? nspl : 0), (uint32_t)s);
+    if (tid == 0) sfn[blockIdx.x] = SlotFn<T>{klo, sh, scale};
 }
 
 template <typename T>
@@ -870,10 +979,13 @@ __global__ void __launch_bounds__(SB_LT<T>, SB_LT<T> / 128) sb_local_kernel(T *_
         const uint32_t s = tid + k * LT;
         key[k] = s - m < c.len ? src[s] : T(0);  // (s < m wraps)
     }
-    load_sub_tables<T>(b, c.b, SS, spl_g, rng_g, spl, rng);
+    const SlotFn<T> f = sfn[c.b];
+    // a bucket on the arithmetic map (workgroup-uniform: a chunk lies in one bucket) needs no table
+    bool arith = false;
+    if constexpr (SB_ARITH<T>) arith = f.scale != 0;
+    if (!arith) load_sub_tables<T>(b, c.b, SS, spl_g, rng_g, spl, rng);
 #pragma unroll
     for (int q = 0; q < PER; ++q) hist[PER * tid + q] = 0;
-    const SlotFn<T> f = sfn[c.b];
     // sorted or reversed input (the first level's bk::BkMap.hot): a wave's consecutive keys share
     // a sub-bucket, counted with one atomic (bk::bucket_bump); 2^30 sorted int32 sub level 4.3 -> 2.1 ms
     const bool hotf = hotp != nullptr && *hotp != 0;
@@ -886,7 +998,41 @@ __global__ void __launch_bounds__(SB_LT<T>, SB_LT<T> / 128) sb_local_kernel(T *_
     constexpr int G = sizeof(T) == 4 ? SB_G32 : SB_G64;
     // a whole chunk: only the first and last slot rows can fall outside it
     const bool whole = c.len == (uint32_t)CHL;
-    if constexpr (G == 1) {
+    if (arith) {
+        // The sub-bucket is arithmetic on the key: no table read, so a key's only LDS round trip is
+        // its rank atomic, and the thread's KPT atomics go out together and are waited for once (the
+        // sampled path's chain of three dependent round trips runs one key at a time).
+        if constexpr (SB_ARITH<T>) {
+            uint32_t jv[KPT];
+#pragma unroll
+            for (int k = 0; k < KPT; ++k) jv[k] = arith_sub(key[k], f.klo, f.scale, (uint32_t)ns);
+            if (hotf) {
+#pragma unroll
+                for (int k = 0; k < KPT; ++k) {
+                    const uint32_t s = tid + k * LT;
+                    pk[k] = jv[k] | bk::bucket_bump<true>(hist, (int)jv[k], s - m < c.len) << 10;
+                }
+            } else {
+                // (a key past the chunk adds 0 to a lane-spread counter: no branch between the atomics)
+                uint32_t rk[KPT];
+                if (whole) {
+#pragma unroll
+                    for (int k = 0; k < KPT; ++k) {
+                        const bool act = (k > 0 && k + 1 < KPT) || (uint32_t)(tid + k * LT) - m < c.len;
+                        rk[k] = atomicAdd(&hist[act ? jv[k] : (uint32_t)lane], act ? 1u : 0u);
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < KPT; ++k) {
+                        const bool act = (uint32_t)(tid + k * LT) - m < c.len;
+                        rk[k] = atomicAdd(&hist[act ? jv[k] : (uint32_t)lane], act ? 1u : 0u);
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < KPT; ++k) pk[k] = jv[k] | rk[k] << 10;
+            }
+        }
+    } else if constexpr (G == 1) {
         if (hotf) {
 #pragma unroll
             for (int k = 0; k < KPT; ++k) {

@@ -1893,7 +1893,7 @@ struct SubArena {
     uint32_t *cnt, *offs;
     void *tt;          // GTile (local) or TileRef (scatter)
     sb::Ovf *ovf;
-    uint32_t *num;     // tiles, merge records
+    uint32_t *num;     // tiles, merge records; [2], [3]: sb_splitter_kernel's counters (actr)
     bk::TileRef *stl;  // sample tiles, then their count
     uint2 *pcs;        // local path: piece tables
     FillSeg<T> *fill;
@@ -1922,7 +1922,7 @@ static size_t sub_arena(const SubArgs<T> &a, const SubPlan<T> &p, uintptr_t base
     take(A.offs, p.local ? 0 : p.nch * SS * 4);
     take(A.tt, p.tmax * sizeof(GTile));
     take(A.ovf, p.nsubs * sizeof(Ovf));
-    take(A.num, 8);
+    take(A.num, 16);
     take(A.stl, B * sizeof(bk::TileRef) + 16);
     take(A.pcs, p.local ? p.tcap * p.PS * sizeof(uint2) : 0);
     take(A.fill, a.pm || a.fill_keys ? B * sizeof(FillSeg<T>) : 0);
@@ -2106,7 +2106,7 @@ static int sub_stage(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T> &p, S
     DSORT_HIP(ctx, hipMemcpyAsync(A.bi, h, B * sizeof(BInfo), hipMemcpyHostToDevice, ctx->side));
     if (nch) DSORT_HIP(ctx, hipMemcpyAsync(A.ch, h + h_ch, nch * sizeof(Chunk), hipMemcpyHostToDevice, ctx->side));
     DSORT_HIP(ctx, hipMemcpyAsync(A.stl, hst, B * sizeof(bk::TileRef) + 16, hipMemcpyHostToDevice, ctx->side));
-    DSORT_HIP(ctx, hipMemsetAsync(A.num, 0, 8, ctx->side));
+    DSORT_HIP(ctx, hipMemsetAsync(A.num, 0, 16, ctx->side));
     if (nfill)
         DSORT_HIP(ctx, hipMemcpyAsync(A.fill, h + h_fill, nfill * sizeof(FillSeg<T>), hipMemcpyHostToDevice, ctx->side));
     DSORT_HIP(ctx, hipEventRecord(ctx->side_ev, ctx->side));
@@ -2160,7 +2160,7 @@ static int sub_splitters(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T> &
         rc = tile_sort<int64_t, false>(ctx, A.cmp, A.cmp, p.nsmp, stl4, pnst, sb::Gather{}, nst, s, false);
         if (rc) return rc;
         hipLaunchKernelGGL(sb_splitter_kernel<T>, dim3((unsigned)B), dim3(SB_MAXS), 0, s, A.cmp, A.smp, A.bi, A.ch, p.os,
-                           p.SS, A.spl, A.rng, A.sfn, A.stot);
+                           p.SS, A.spl, A.rng, A.sfn, A.stot, (int)ctx->opt.sub_arith, A.num + 2);
         DSORT_HIP(ctx, hipGetLastError());
     } else if (A.stot) {
         DSORT_HIP(ctx, hipMemsetAsync(A.stot, 0, (size_t)B * p.SS * 4, s));
@@ -2211,7 +2211,7 @@ static int sub_local_path(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T> 
                            static_cast<const Chunk *>(A.ch), A.cnt, SS, A.pcs, PS, (uint32_t)tcap);
         DSORT_HIP(ctx, hipGetLastError());
     }
-    DSORT_HIP(ctx, hipMemcpyAsync(A.hn, num, 8, hipMemcpyDeviceToHost, s));
+    DSORT_HIP(ctx, hipMemcpyAsync(A.hn, num, 16, hipMemcpyDeviceToHost, s));
     DSORT_HIP(ctx, hipEventRecord(ctx->sub_ev, s));
     // The tile sort of the first `early` tiles goes out behind the count's read-back, before the
     // host waits for it: every tile holds at most TILE keys, so there are at least (keys in
@@ -2245,6 +2245,8 @@ static int sub_local_path(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T> 
         overflow = true;
         return DSORT_OK;
     }
+    ctx->sub_arith_n[0] += A.hn[2];
+    ctx->sub_arith_n[1] += A.hn[3];
     // every tile's piece table
     if (ntiles && !pieces_in_scan && !pieces_early) {
         hipLaunchKernelGGL(sb_pieces_kernel, dim3((unsigned)ceil_div(ntiles, 4)), dim3(256), 0, s, gtiles, num,
@@ -2302,7 +2304,7 @@ static int sub_scatter_path(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T
     hipLaunchKernelGGL(sb_scan_kernel<false>, dim3((unsigned)B), dim3(SB_MAXS), 0, s, A.bi, SS, A.cnt, A.offs, TILE,
                        (int)ALIGN, mis, 0u, A.tt, num, A.ovf, num + 1, (uint32_t)p.tmax, nullptr, nullptr, 0u, 0u, nullptr);
     DSORT_HIP(ctx, hipGetLastError());
-    DSORT_HIP(ctx, hipMemcpyAsync(A.hn, num, 8, hipMemcpyDeviceToHost, s));
+    DSORT_HIP(ctx, hipMemcpyAsync(A.hn, num, 16, hipMemcpyDeviceToHost, s));
     DSORT_HIP(ctx, hipEventRecord(ctx->sub_ev, s));
     // 3. scatter into d_keys (the host reads the tile count meanwhile), tile sort in place
     if (nch) {
@@ -2314,6 +2316,8 @@ static int sub_scatter_path(dsort_ctx *ctx, const SubArgs<T> &a, const SubPlan<T
     if (int rc_ = sync_event(ctx, ctx->sub_ev, "tile count")) return rc_;
     const uint32_t ntiles = A.hn[0], novf = A.hn[1];
     if (ntiles > p.tmax || novf > p.nsubs) return set_err(ctx, DSORT_EHIP, "sub-bucket packing overflow");
+    ctx->sub_arith_n[0] += A.hn[2];
+    ctx->sub_arith_n[1] += A.hn[3];
     fault_point(ctx, s, 1);  // second-level partition done
     ctx->stats.merge_passes = 0;
     if (ntiles) {
@@ -2535,6 +2539,7 @@ static int first_level(dsort_ctx *ctx, const T *d_in, uint64_t n, uint64_t ioff,
 // The stats and events of a bucketed sort start after its nested splitter sort.
 static int bucketed_stats_start(dsort_ctx *ctx, uint64_t n, int tile, hipStream_t s, bool timed) {
     ctx->bk_hot = nullptr;  // (set by this sort's first level, if it runs one)
+    ctx->sub_arith_n[0] = ctx->sub_arith_n[1] = 0;
     ctx->stats = fresh_stats();
     ctx->stats.keys_in = ctx->stats.keys_out = n;
     ctx->stats.tile_sort_keys = n;
@@ -3187,6 +3192,22 @@ static int wave_merge(dsort_ctx *ctx, const T *d_in, const size_t *lens, int k, 
 }
 
 }  // namespace wv
+
+// Not part of the ABI (like the stamps below): the second level's arithmetic sub-bucket map
+// (dsort_sub.h).  mode: -1 per bucket by the sample rule (default), 0 off, 2 (tests) every bucket whose
+// span allows it.  out[0] = buckets of several sub-buckets in the context's last bucketed sort (every
+// wave of a bucket exchange), out[1] = those of them that took the map.
+extern "C" int dsort_debug_sub_arith_mode(dsort_ctx *ctx, int mode) {
+    if (!ctx || (mode != -1 && mode != 0 && mode != 2)) return DSORT_EINVAL;
+    ctx->opt.sub_arith = mode;
+    return DSORT_OK;
+}
+extern "C" int dsort_debug_sub_arith(const dsort_ctx *ctx, uint32_t out[2]) {
+    if (!ctx || !out) return DSORT_EINVAL;
+    out[0] = ctx->sub_arith_n[0];
+    out[1] = ctx->sub_arith_n[1];
+    return DSORT_OK;
+}
 
 #ifdef DSORT_STAMPS
 extern "C" int dsort_debug_stamps(void *host, size_t bytes) {

@@ -538,6 +538,22 @@ class Context:
         self.check(self.lib.dsort_get_option(self.h, self._opt(name), ctypes.byref(v)))
         return v.value
 
+    # Not part of the ABI (debug entries of csrc/dsort_wave.hip, outside include/dsort.h): the second
+    # level's arithmetic sub-bucket map.
+    def sub_arith_mode(self, mode):
+        """-1 = per bucket by the sample rule (default), 0 = off, 2 = every bucket whose span allows it (tests)."""
+        f = self.lib.dsort_debug_sub_arith_mode
+        f.restype, f.argtypes = ctypes.c_int, [P, ctypes.c_int]
+        self.check(f(self.h, int(mode)))
+
+    def sub_arith_counts(self):
+        """(buckets of several sub-buckets, those on the arithmetic map) of the last bucketed sort."""
+        out = (ctypes.c_uint32 * 2)()
+        f = self.lib.dsort_debug_sub_arith
+        f.restype, f.argtypes = ctypes.c_int, [P, P]
+        self.check(f(self.h, ctypes.cast(out, P)))
+        return int(out[0]), int(out[1])
+
     @contextlib.contextmanager
     def options(self, **kw):
         """Sets options for the body of a with-statement and restores the previous values."""

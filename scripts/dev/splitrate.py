@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Over-tile sub-bucket rate of the default sort (dev tool): sorts 2^30 uniform int32 keys for
-`--seeds` seeds and prints each sort's sub_split_subbuckets, merge passes and device time.
+`--seeds` seeds and prints each sort's sub_split_subbuckets, merge passes, the buckets on the arithmetic
+sub-bucket map and device time.
    splitrate.py [--seeds K] [--keys N] [--opt name=value ...]   (DSORT_LIB selects a build)"""
 import argparse
 import os
@@ -28,6 +29,7 @@ for sd in range(a.seeds):
     ctx.sort_dev(t, o)
     st = ctx.stats()
     splits += st["sub_split_subbuckets"]
+    many, took = ctx.sub_arith_counts()  # (buckets of several sub-buckets, those on the arithmetic map)
     print(f"seed {sd}: split {st['sub_split_subbuckets']} passes {st['merge_passes']} "
-          f"fallback {st['sub_scatter_fallback']} total {st['total_ms']:.3f} ms", flush=True)
+          f"fallback {st['sub_scatter_fallback']} on the map {took} of {many} total {st['total_ms']:.3f} ms", flush=True)
 print(f"split sub-buckets: {splits} in {a.seeds} sorts")
