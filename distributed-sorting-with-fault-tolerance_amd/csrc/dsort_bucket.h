@@ -12,7 +12,8 @@
 // Kernels (all keyed by the composite c = (key, input index), unique per key):
 //   bucket_sample_kernel / pair_*   s regular samples -> composites (sorted by the int64 sort)
 //   bucket_splitter_kernel          splitter b = sample (b+1)*s/B - 1; padded with +inf to BP
-//   bucket_slotmap_kernel           the lookups' slot map (int64: linear or log, one-key slots)
+//   bucket_slotmap_kernel           the lookups' slot map (int64: linear or log, one-key slots); int32:
+//                                   whether the buckets are arithmetic on the key instead (BkMap.ar)
 //   bucket_hist_kernel              per workgroup range: keys per bucket (LDS atomics)
 //   bucket_colsum_kernel            per 64 workgroups: column sums        } exclusive scan of the
 //   bucket_scan_kernel              one workgroup: chunk prefixes, bucket } histograms in (bucket,
@@ -185,7 +186,51 @@ struct BkMap {
     uint32_t r2s;
     uint32_t r2lo;  // flipped key one below the refined slot's first splitter's (or the slot's start)
     uint32_t r2sh;  // sub-slot = (flipped key - r2lo) >> r2sh, clamped to [0, BK_R2)
+    // int32, keys spread evenly over the samples' range: the bucket is arith_bucket(key) (below), no
+    // slot table and no splitter read; L.spl then holds the map's synthetic splitters
+    uint32_t ar;
+    uint32_t arlo;     // the smallest sample key (an int32)
+    uint32_t arscale;  // arith_scale(the samples' key range, B)
 };
+
+// The arithmetic map (int32): n equal key widths over [klo, klo + span],
+//     arith_part(key) = min(umulhi(max(key - klo, 0), scale), n - 1),  scale = floor(n 2^32 / (span + 1)),
+// monotone in the key, keys below the range in part 0 and keys above it running on to n - 1.  Its
+// SYNTHETIC splitter j is (the largest key with arith_part <= j, index UINT32_MAX): a lookup over
+// those splitters returns arith_part(key) for every key at every index below UINT32_MAX, so whatever
+// reads the splitters reads them as before and only the partition kernels take the short cut.
+// span >= 2 n (arith_span_ok) makes scale < 2^31, hence the splitters' offsets
+// ceil((j + 1) 2^32 / scale) - 1 strictly increasing; only the last of them can pass the range
+// (scale is rounded down), and only that one can pass INT32_MAX, where it is capped -- no key lies
+// above it then, and no two splitters are equal.  The first level uses it over the whole sort's
+// samples (BkMap.ar, B buckets), the second level per bucket (dsort_sub.h, sub-buckets).
+template <typename T> constexpr bool BK_ARITH = sizeof(T) == 4;
+__host__ __device__ __forceinline__ bool arith_span_ok(uint32_t span, uint32_t n) { return span >= 2 * n; }
+__host__ __device__ __forceinline__ uint32_t arith_scale(uint32_t span, uint32_t n) {
+    return (uint32_t)(((uint64_t)n << 32) / ((uint64_t)span + 1));
+}
+__host__ __device__ __forceinline__ uint32_t arith_part(int32_t key, int32_t klo, uint32_t scale, uint32_t n) {
+    const uint32_t d = key < klo ? 0u : (uint32_t)key - (uint32_t)klo;
+    const uint32_t j = (uint32_t)(((uint64_t)d * scale) >> 32);
+    return j < n - 1 ? j : n - 1;
+}
+// the key of synthetic splitter j (j < n - 1)
+__host__ __device__ __forceinline__ int32_t arith_splitter_key(int32_t klo, uint32_t scale, uint32_t j) {
+    const uint64_t d = ((((uint64_t)j + 1) << 32) + scale - 1) / scale - 1;
+    const int64_t k = (int64_t)klo + (int64_t)d;
+    return k < (int64_t)INT32_MAX ? (int32_t)k : INT32_MAX;
+}
+// The first level's bucket of a key on the map.
+__host__ __device__ __forceinline__ int arith_bucket(int32_t key, const BkMap &m, int B) {
+    return (int)arith_part(key, (int32_t)m.arlo, m.arscale, (uint32_t)B);
+}
+// The rule a sort takes the map by, beyond the span and the plain fixed map (bucket_slotmap_kernel):
+// no arithmetic bucket holds more than 3/2 os of the B os samples.  The second level switches to
+// 16384-key tiles above buckets of twice the mean; 1.5x by samples leaves about 3.5 sampling standard
+// deviations to that at os = 128 (uniform keys: Poisson(128) counts, P(> 192) ~ 1e-8 per bucket).
+__host__ __device__ __forceinline__ bool arith_bucket_full(uint32_t samples, uint32_t os) {
+    return 2 * (uint64_t)samples > 3 * (uint64_t)os;
+}
 // The refined slot's table follows the map (bucket_slotmap_kernel writes both): entry i = the
 // splitters below sub-slot i (bits 0-13), "key implied" (bit 14: the sub-slot holds one key value),
 // one-key flag (bit 15: its >= 2 splitters hold one key K), the splitters below sub-slot i + 1 (bits
@@ -482,9 +527,17 @@ __device__ __forceinline__ int bucket_fast(const typename Comp<T>::C *spl, const
 
 // The slot map of a sort: linear unless the log map leaves fewer distinct splitter keys in its
 // most crowded slot (one workgroup; out = BkMap).
+// int32, the arithmetic map (BkMap.ar): smp (not null: the caller allows the map) = the ns = B os sorted
+// sample composites the splitters were taken from.  arith: -1 = the sort takes the map when the sampled
+// choice is the plain fixed map (no adaptive map, refined slot, one-key slot or runs), the samples'
+// range allows it (arith_span_ok) and no arithmetic bucket is too full of samples
+// (arith_bucket_full); 0 = never; 2 (tests) = whenever the range allows it.  A sort on the map gets
+// its splitters replaced by the map's synthetic ones.
 template <typename T>
-__global__ void __launch_bounds__(BK_MAXB) bucket_slotmap_kernel(const typename Comp<T>::C *__restrict__ spl,
-                                                                  int B, uint64_t n, BkMap *__restrict__ out) {
+__global__ void __launch_bounds__(BK_MAXB) bucket_slotmap_kernel(typename Comp<T>::C *spl, int B, uint64_t n,
+                                                                  BkMap *__restrict__ out,
+                                                                  const typename Comp<T>::C *smp, uint32_t ns, int os,
+                                                                  int arith) {
     using CT = Comp<T>;
     using U = typename CT::U;
     __shared__ uint32_t cnt[2][BK_SLOTS];
@@ -558,11 +611,54 @@ __global__ void __launch_bounds__(BK_MAXB) bucket_slotmap_kernel(const typename 
             for (int i = j; i < BK_SLOTS; i += blockDim.x)
                 if ((uint32_t)i != r2slot && dst[0][i] >= 2) atomicMax(&cost2, tot[0][i]);
         __syncthreads();
-        const bool refine = r2slot != ~0u && cost2 <= cost[qa];
-        const bool fixed = cost[0] <= AD_MIX || refine;
+        const bool refine_s = r2slot != ~0u && cost2 <= cost[qa];
+        const bool fixed_s = cost[0] <= AD_MIX || refine_s;
+        // The arithmetic map (workgroup-uniform up to ar_on): the rule is counted on the sorted
+        // samples, one binary search per bucket boundary -- samples of bucket b = those above
+        // synthetic splitter b - 1 and not above splitter b.
+        __shared__ uint32_t ar_ub[BK_MAXB];
+        __shared__ uint32_t ar_bad;
+        bool ar_on = false;
+        int32_t ar_klo = 0;
+        uint32_t ar_scale = 0;
+        if constexpr (BK_ARITH<T>) {
+            if (smp && arith != 0 && ns > 0 && B >= 2) {
+                ar_klo = CT::key_of(smp[0]);
+                const uint32_t span = (uint32_t)CT::key_of(smp[ns - 1]) - (uint32_t)ar_klo;
+                const bool plain = fixed_s && !refine_s && ndup == 0 && !bucket_runs_hint<T>(nasc, ndup, nsp);
+                if (arith_span_ok(span, (uint32_t)B) && (arith > 0 || plain)) {
+                    ar_scale = arith_scale(span, (uint32_t)B);
+                    ar_on = true;
+                }
+            }
+            if (ar_on && arith < 0) {
+                if (j == 0) ar_bad = 0;
+                uint32_t ub = ns;
+                if (j < B - 1) {
+                    const int32_t K = arith_splitter_key(ar_klo, ar_scale, (uint32_t)j);
+                    uint32_t lo = 0, hi = ns;
+                    while (lo < hi) {  // the samples with key <= K
+                        const uint32_t mid = (lo + hi) >> 1;
+                        if (CT::key_of(smp[mid]) <= K) lo = mid + 1;
+                        else hi = mid;
+                    }
+                    ub = lo;
+                }
+                if (j < B) ar_ub[j] = ub;
+                __syncthreads();
+                if (j < B && arith_bucket_full(ub - (j ? ar_ub[j - 1] : 0u), (uint32_t)os)) ar_bad = 1;
+                __syncthreads();
+                if (ar_bad) ar_on = false;
+            }
+        }
+        // (forced on, arith = 2: the map replaces whatever the samples chose)
+        const bool refine = refine_s && !ar_on, fixed = fixed_s || ar_on;
         if (j == 0) {
             if (!refine) r2slot = ~0u;
             BkMap r = fixed ? am[0] : am[qa];
+            r.ar = ar_on ? 1u : 0u;
+            r.arlo = (uint32_t)ar_klo;
+            r.arscale = ar_on ? ar_scale : 0u;
             r.ad = r.ulo != 0 || r.mode != 0 || r.sh != (uint32_t)(CT::KB - BK_SLOTB) ? 1u : 0u;
             r.ids = 0;  // (int32 stores no bucket ids, BkIds)
             r.hot = bucket_runs_hint<T>(nasc, ndup, nsp);
@@ -635,6 +731,12 @@ __global__ void __launch_bounds__(BK_MAXB) bucket_slotmap_kernel(const typename 
                 const bool implied = rm.r2sh == 0 && i > 0 && i + 1 < BK_R2;
                 tab[i] = c0 | (implied ? BK_R2_IMPLIED : 0u) | (uint32_t)one << 15 | c1 << 16;
             }
+        }
+        // on the arithmetic map: the synthetic splitters (every read of the sampled ones lies before
+        // the barrier above), so the lookups, the tile sort's bounds, the host's pure-bucket test and
+        // the second level see the buckets the map makes
+        if constexpr (BK_ARITH<T>) {
+            if (rm.ar && j < nsp) spl[j] = CT::make(arith_splitter_key((int32_t)rm.arlo, rm.arscale, (uint32_t)j), 0xFFFFFFFFull);
         }
         return;
     }
@@ -784,8 +886,12 @@ __host__ __forceinline__ int bucket_wg_subs(uint64_t n) {
 // counts[g * B + b] = keys of workgroup g's subs sub-tiles in bucket b.  (The same slot table as
 // the scatter's: the one-key slots must agree.)  ioff: the composite index of in[0] (the multi-GPU
 // path: this rank's first key in the global order; 0 on one GPU).  AD (int32): the instance of the
-// adaptive map (BkMap.ad; the host launches the one the slot map chose).
-template <typename T, bool AD = false>
+// adaptive map (BkMap.ad; the host launches the one the slot map chose).  AR (int32): the instance of
+// the arithmetic map (BkMap.ar), launched likewise.  (As a fourth workgroup-uniform branch of the one
+// kernel's loop it cost the other branches 0.55-0.65 ms at 2^30 keys -- sorted input 1.03 -> 1.60 ms,
+// the refined slot 1.26 -> 1.94 ms, profiles/ab_bucket_arith.log -- and in a loop of its own the
+// kernel took 67 VGPRs: one workgroup per CU.)
+template <typename T, bool AD = false, bool AR = false>
 __global__ void __launch_bounds__(BK_T, 2) bucket_hist_kernel(const T *__restrict__ in, uint64_t n,
                                                               const typename Comp<T>::C *__restrict__ spl_g,
                                                               const BkMap *__restrict__ map, int B, int BP,
@@ -795,24 +901,50 @@ __global__ void __launch_bounds__(BK_T, 2) bucket_hist_kernel(const T *__restric
     constexpr bool ADP = CT::ADAPT || AD;
     constexpr int KPT = Geo<T>::KPT, SUB = BK_T * KPT;
     static_assert(!BkIds<T>::ON || KPT % BkIds<T>::PER_WORD == 0, "bucket ids: whole words per thread");
-    __shared__ typename CT::C spl[BK_MAXB + 1];
-    __shared__ uint32_t rng[BK_SLOTS];
+    static_assert(!AR || (BK_ARITH<T> && !AD), "the arithmetic map: int32 on the plain fixed map");
+    // (the arithmetic map needs no splitters and no slot table)
+    __shared__ typename CT::C spl[AR ? 1 : BK_MAXB + 1];
+    __shared__ uint32_t rng[AR ? 1 : BK_SLOTS];
     const BkMap m = *map;
-    if (!ADP && m.ad) return;  // (int32: the adaptive map's instance counts this sort, first_level)
+    if (!ADP && !AR && (m.ad || m.ar)) return;  // (int32: another instance counts this sort, first_level)
     __shared__ uint32_t hist[BK_MAXB];
     __shared__ uint32_t tab2[ADP ? 1 : BK_R2];  // (the refined slot's table, BkMap.r2s)
-    load_splitters<T>(spl_g, BP, spl);
+    if constexpr (!AR) load_splitters<T>(spl_g, BP, spl);
     for (int b = threadIdx.x; b < B; b += BK_T) hist[b] = 0;
     if (!ADP && m.r2s)
         for (int i = threadIdx.x; i < BK_R2; i += BK_T) tab2[i] = bk_tab2(map)[i];
     __syncthreads();
-    build_slots<T, false, BK_SLOTB, ADP>(spl, BP, m, rng);  // (the packed table measured 0.78 -> 0.93 ms here)
-    __syncthreads();
+    if constexpr (!AR) {
+        build_slots<T, false, BK_SLOTB, ADP>(spl, BP, m, rng);  // (the packed table measured 0.78 -> 0.93 ms here)
+        __syncthreads();
+    }
     const uint64_t g0 = (uint64_t)blockIdx.x * subs * SUB;
     // the next sub-tile's keys are loaded while the current one is counted (two workgroups per CU
     // alone left the loads' latency exposed: 0.79 ms for 4.3 GB)
     T nxt[KPT];
     load_sub<T, KPT, false>(in, g0 + threadIdx.x, n, g0 + SUB, nxt);
+    if constexpr (AR) {
+        // the bucket is arithmetic on the key, and a thread's atomics go out back to back
+#pragma unroll 1
+        for (int sub = 0; sub < subs; ++sub) {
+            const uint64_t b0 = g0 + (uint64_t)sub * SUB + threadIdx.x;
+            int bb[KPT];
+#pragma unroll
+            for (int k = 0; k < KPT; ++k) bb[k] = arith_bucket((int32_t)nxt[k], m, B);
+            if (sub + 1 < subs) load_sub<T, KPT, false>(in, b0 + SUB, n, b0 - threadIdx.x + 2 * SUB, nxt);
+            if (b0 - threadIdx.x + SUB <= n) {  // (a whole sub-tile: workgroup-uniform)
+#pragma unroll
+                for (int k = 0; k < KPT; ++k) atomicAdd(&hist[bb[k]], 1u);
+            } else {
+#pragma unroll
+                for (int k = 0; k < KPT; ++k)
+                    if (b0 + (uint64_t)k * BK_T < n) atomicAdd(&hist[bb[k]], 1u);
+            }
+        }
+        __syncthreads();
+        for (int b = threadIdx.x; b < B; b += BK_T) counts[(uint64_t)blockIdx.x * B + b] = hist[b];
+        return;
+    }
 #pragma unroll 1
     for (int sub = 0; sub < subs; ++sub) {
         const uint64_t b0 = g0 + (uint64_t)sub * SUB + threadIdx.x;
@@ -1089,7 +1221,10 @@ __device__ unsigned long long g_bkstamps[8192 * 16];
 // (one kernel with a run-time branch: uniform int64 scatter 5.29 -> 5.84 ms).
 // HT: the instance for input with runs of one bucket (BkMap.hot: sorted, reversed), which enters a
 // long line stream in the line map with the owner's whole wave.
-template <typename T, bool IDS, bool AD = false, bool HT = false>
+// AR (int32): the instance of the arithmetic map (BkMap.ar; the host launches it): the bucket is
+// arith_bucket(key) -- no slot table, no splitters staged, and a thread's rank atomics in flight
+// together behind one wait.
+template <typename T, bool IDS, bool AD = false, bool HT = false, bool AR = false>
 __global__ void __launch_bounds__(BK_T) bucket_scatter_lines_kernel(const T *__restrict__ in, uint64_t n,
                                                                     const typename Comp<T>::C *__restrict__ spl_g,
                                                                     const BkMap *__restrict__ map, int B, int BP, int subs,
@@ -1099,6 +1234,7 @@ __global__ void __launch_bounds__(BK_T) bucket_scatter_lines_kernel(const T *__r
     using CT = Comp<T>;
     constexpr bool ADP = CT::ADAPT || AD;  // (AD: int32's adaptive-map instance, BkMap.ad)
     static_assert(!IDS || BkIds<T>::ON, "bucket ids of this key width");
+    static_assert(!AR || (BK_ARITH<T> && !IDS && !AD && !HT), "the arithmetic map: int32 on the plain fixed map");
     using G = LineGeo<T>;
     using V = typename std::conditional<sizeof(T) == 4, int4, longlong2>::type;
     constexpr int KPT = Geo<T>::KPT, SUB = G::SUB, LK = G::LK, KPL = G::KPL;
@@ -1108,7 +1244,7 @@ __global__ void __launch_bounds__(BK_T) bucket_scatter_lines_kernel(const T *__r
     // from global memory on its rare slow path), which leaves lk room for 16 keys per thread
     constexpr bool SPL_LK = !CT::ADAPT;
     __shared__ typename CT::C spl_own[SPL_LK || IDS ? 1 : BK_MAXB + 1];
-    __shared__ uint32_t rng[IDS ? 1 : BK_SLOTS];
+    __shared__ uint32_t rng[IDS || AR ? 1 : BK_SLOTS];
     __shared__ uint32_t hist[BK_MAXB];               // sub-tile histogram, then the LDS starts
     __shared__ uint2 st[BK_MAXB];                    // per bucket: LDS start | first line << 16, vc|ph|pure|L
     __shared__ uint32_t sgb[BK_MAXB];                // per bucket: global index of stream entry 0
@@ -1151,10 +1287,10 @@ __global__ void __launch_bounds__(BK_T) bucket_scatter_lines_kernel(const T *__r
     }
     const BkMap m = *map;
     // (the refined slot's table, BkMap.r2s: in the LDS the scatter has left)
-    __shared__ uint32_t tab2s[ADP || IDS ? 1 : BK_R2];
-    const uint32_t *tab2 = ADP || IDS ? nullptr : tab2s;
+    __shared__ uint32_t tab2s[ADP || IDS || AR ? 1 : BK_R2];
+    const uint32_t *tab2 = ADP || IDS || AR ? nullptr : tab2s;
     if (BkIds<T>::ON && (m.ids != 0) != IDS) return;  // (workgroup-uniform: the other variant's sort)
-    if (!IDS) {
+    if (!IDS && !AR) {
         load_splitters<T>(spl_g, BP, spl);
         if (!ADP && m.r2s)
             for (int i = tb; i < BK_R2; i += BK_T) tab2s[i] = bk_tab2(map)[i];
@@ -1198,6 +1334,9 @@ __global__ void __launch_bounds__(BK_T) bucket_scatter_lines_kernel(const T *__r
         if constexpr (IDS) {
 #pragma unroll
             for (int k = 0; k < KPT; ++k) sl[k] = (nid[k / PW] >> (BkIds<T>::BITS * (k % PW))) & BkIds<T>::MASK;
+        } else if constexpr (AR) {
+#pragma unroll
+            for (int k = 0; k < KPT; ++k) sl[k] = (uint32_t)arith_bucket((int32_t)key[k], m, B);
         } else {
             slots_at<T, KPT, ADP>(m, key, sl);
         }
@@ -1206,7 +1345,24 @@ __global__ void __launch_bounds__(BK_T) bucket_scatter_lines_kernel(const T *__r
             if constexpr (IDS) load_ids(s0 + SUB);
         }
         BKST(6);  // (the sub-tile's keys in, their slots)
-        if (m.hot) {  // (runs of one bucket: aggregated ranks, bucket_runs_hint)
+        if constexpr (AR) {
+            // (sl holds the buckets.)  A whole sub-tile: the thread's KPT rank atomics are issued
+            // together and waited for once; the guarded last sub-tile takes the per-key form.  No
+            // bucket of the map is pure (its splitters are strictly increasing), so nothing is dropped.
+            if (s0 + SUB <= n && !anyp) {
+#pragma unroll
+                for (int k = 0; k < KPT; ++k) pk[k] = atomicAdd(&hist[sl[k]], 1u);
+#pragma unroll
+                for (int k = 0; k < KPT; ++k) pk[k] |= sl[k] << 16;
+            } else {
+#pragma unroll
+                for (int k = 0; k < KPT; ++k) {
+                    const uint64_t i = s0 + tb + (uint64_t)k * BK_T;
+                    pk[k] = ~0u;
+                    if (i < n && !dropped((int)sl[k])) pk[k] = atomicAdd(&hist[sl[k]], 1u) | sl[k] << 16;
+                }
+            }
+        } else if (m.hot) {  // (runs of one bucket: aggregated ranks, bucket_runs_hint)
 #pragma unroll
             for (int k = 0; k < KPT; ++k) {
                 const uint64_t i = s0 + tb + (uint64_t)k * BK_T;

@@ -161,6 +161,8 @@ struct dsort_opts {
     int64_t sub_arith = -1;         // not an ABI option (dsort_debug_sub_arith_mode): the second level's arithmetic
                                     // sub-bucket map: -1 per bucket by the sample rule, 0 off, 2 (tests) every
                                     // bucket whose span allows it
+    int64_t bk_arith = -1;          // likewise (dsort_debug_bucket_arith_mode): the first level's arithmetic
+                                    // bucket map: -1 by the rule, 0 off, 2 (tests) whenever the span allows it
 };
 
 // The context.  One per host thread, bound to one device.
@@ -286,6 +288,8 @@ struct dsort_ctx {
     const uint32_t *bk_hot = nullptr;  // the last first level's runs flag (device, BkMap.hot)
     uint32_t sub_arith_n[2] = {0, 0};  // the last bucketed sort: buckets of several sub-buckets, and those of
                                        // them on the arithmetic map (dsort_debug_sub_arith)
+    uint32_t bk_arith_on = 0;          // the last bucketed sort's first level ran on the arithmetic bucket map
+                                       // (dsort_debug_bucket_arith)
     int ev_off = 0;               // kWave0Offset while the bucket exchange's first wave runs its second
                                   // level and tile sort (dsort_get_stats adds the two waves up)
     int ev_done = dsort::kEvLocalDone;  // the stage event a sort's second level records at its end (the

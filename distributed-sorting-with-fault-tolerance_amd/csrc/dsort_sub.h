@@ -133,21 +133,13 @@ template <> struct __attribute__((aligned(16))) Spl<int64_t> {
 // can pass the bucket's range (scale is rounded down), and only that one can pass INT32_MAX, where it
 // is capped -- no key lies above it then, and no two splitters are equal.
 // int64 keys stay on the sampled path: a 64-bit multiply-high per key was not tried (SB_ARITH).
-template <typename T> constexpr bool SB_ARITH = sizeof(T) == 4;
-__host__ __device__ __forceinline__ bool arith_span_ok(uint32_t span, uint32_t nsub) { return span >= 2 * nsub; }
-__host__ __device__ __forceinline__ uint32_t arith_scale(uint32_t span, uint32_t nsub) {
-    return (uint32_t)(((uint64_t)nsub << 32) / ((uint64_t)span + 1));
-}
+// (The map's functions are the first level's, dsort_bucket.h: one form for both levels.)
+template <typename T> constexpr bool SB_ARITH = bk::BK_ARITH<T>;
+using bk::arith_scale;
+using bk::arith_span_ok;
+using bk::arith_splitter_key;
 __host__ __device__ __forceinline__ uint32_t arith_sub(int32_t key, int32_t klo, uint32_t scale, uint32_t nsub) {
-    const uint32_t d = key < klo ? 0u : (uint32_t)key - (uint32_t)klo;
-    const uint32_t j = (uint32_t)(((uint64_t)d * scale) >> 32);
-    return j < nsub - 1 ? j : nsub - 1;
-}
-// the key of synthetic splitter j (j < nsub - 1)
-__host__ __device__ __forceinline__ int32_t arith_splitter_key(int32_t klo, uint32_t scale, uint32_t j) {
-    const uint64_t d = ((((uint64_t)j + 1) << 32) + scale - 1) / scale - 1;
-    const int64_t k = (int64_t)klo + (int64_t)d;
-    return k < (int64_t)INT32_MAX ? (int32_t)k : INT32_MAX;
+    return bk::arith_part(key, klo, scale, nsub);
 }
 // The rule a bucket takes the map by, beyond the span: none of its arithmetic sub-buckets holds
 // more than SB_ARITH_MAXS * os of the bucket's nsub * os samples, i.e. is predicted above three

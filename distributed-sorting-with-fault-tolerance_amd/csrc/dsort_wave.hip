@@ -2453,17 +2453,23 @@ static int bk_layout(dsort_ctx *ctx, uint64_t n, int B, size_t smp_bytes, BkLayo
 // ioff = the composite index of d_in[0].  `tile` != 0: also the merge path's tile table.
 // compact (the bucket exchange): the keys of pure buckets are dropped and part_out holds the others
 // at the compacted starts (bucket_scan_kernel); hb stays the real starts.
+// arith (int32): L.smp holds the B * bucket_os sorted sample composites the splitters were taken from,
+// and the sort may take the arithmetic map (bk::BkMap.ar), which replaces L.spl by its synthetic
+// splitters.  (The bucket exchange's splitters are global, not this rank's samples': it does not.)
 template <typename T>
 static int first_level(dsort_ctx *ctx, const T *d_in, uint64_t n, uint64_t ioff, T *part_out, T *direct,
                        const BkLayout<T> &L, uint32_t tile, hipStream_t s, bool timed, uint64_t *&hb,
-                       typename bk::Comp<T>::C *&hspl, bool compact = false) {
+                       typename bk::Comp<T>::C *&hspl, bool compact = false, bool arith = false) {
     using namespace bk;
     using C = typename Comp<T>::C;
     const int B = L.B, BP = L.BP;
     int rc;
     hb = ctx->bucket_host.as<uint64_t>();
     hspl = reinterpret_cast<C *>(hb + BK_MAXB + 1);
-    hipLaunchKernelGGL(bucket_slotmap_kernel<T>, dim3(1), dim3(BK_MAXB), 0, s, L.spl, B, n, L.map);
+    const bool ar_ok = BK_ARITH<T> && arith;
+    hipLaunchKernelGGL(bucket_slotmap_kernel<T>, dim3(1), dim3(BK_MAXB), 0, s, L.spl, B, n, L.map,
+                       ar_ok ? reinterpret_cast<const C *>(L.smp) : (const C *)nullptr,
+                       (uint32_t)B * (uint32_t)bucket_os(ctx), bucket_os(ctx), ar_ok ? (int)ctx->opt.bk_arith : 0);
     ctx->bk_hot = &L.map->hot;
     // int32: which map did the splitters choose -- the fixed one (packed lookup) or the adaptive
     // one (many small keys)?  Its kernels are separate instances, so the host reads the choice back
@@ -2486,6 +2492,9 @@ static int first_level(dsort_ctx *ctx, const T *d_in, uint64_t n, uint64_t ioff,
         if (ad)
             hipLaunchKernelGGL((bucket_hist_kernel<T, true>), dim3((unsigned)L.G), dim3(BK_T), 0, s, d_in, n, L.spl,
                                L.map, B, BP, L.subs, L.cnt, ioff, L.ids);
+        else if (BK_ARITH<T> && hm->ar)  // (the arithmetic map's instance, likewise)
+            hipLaunchKernelGGL((bucket_hist_kernel<T, false, BK_ARITH<T>>), dim3((unsigned)L.G), dim3(BK_T), 0, s, d_in,
+                               n, L.spl, L.map, B, BP, L.subs, L.cnt, ioff, L.ids);
     }
     if ((rc = stage_event(ctx, s, timed, kEvHist1))) return rc;
     hipLaunchKernelGGL(bucket_colsum_kernel, dim3((unsigned)L.nchunk), dim3(BK_MAXB), 0, s, L.cnt, (uint32_t)L.G, B,
@@ -2515,7 +2524,15 @@ static int first_level(dsort_ctx *ctx, const T *d_in, uint64_t n, uint64_t ioff,
             hipLaunchKernelGGL((bucket_scatter_lines_kernel<T, false, true>), dim3((unsigned)L.G), dim3(BK_T), 0, s,
                                d_in, n, L.spl, L.map, B, BP, L.subs, L.offs, part_out, direct, ioff, L.ids);
     }
-    if (!ad && !ids) {
+    bool ar = false;
+    if constexpr (BK_ARITH<T>) {
+        ar = !ad && hm->ar != 0;
+        if (ar)  // (int32: the arithmetic map's instance)
+            hipLaunchKernelGGL((bucket_scatter_lines_kernel<T, false, false, false, true>), dim3((unsigned)L.G),
+                               dim3(BK_T), 0, s, d_in, n, L.spl, L.map, B, BP, L.subs, L.offs, part_out, direct, ioff,
+                               L.ids);
+    }
+    if (!ad && !ids && !ar) {
         if (!Comp<T>::ADAPT && hm->hot)  // (int32: runs of one bucket)
             hipLaunchKernelGGL((bucket_scatter_lines_kernel<T, false, false, true>), dim3((unsigned)L.G), dim3(BK_T), 0,
                                s, d_in, n, L.spl, L.map, B, BP, L.subs, L.offs, part_out, direct, ioff, L.ids);
@@ -2533,6 +2550,7 @@ static int first_level(dsort_ctx *ctx, const T *d_in, uint64_t n, uint64_t ioff,
     if (int rc_ = sync_event(ctx, ctx->bucket_ev, "bucket starts")) return rc_;
     if (hb[B] != n) return set_err(ctx, DSORT_EHIP, "bucket partition lost keys");
     ctx->stats.first_level_map = !Comp<T>::ADAPT && !ad ? (hm->r2s ? 3 : 0) : hm->mode == 0 ? 1 : 2;
+    ctx->bk_arith_on = ar ? 1u : 0u;
     return DSORT_OK;
 }
 
@@ -2540,6 +2558,7 @@ static int first_level(dsort_ctx *ctx, const T *d_in, uint64_t n, uint64_t ioff,
 static int bucketed_stats_start(dsort_ctx *ctx, uint64_t n, int tile, hipStream_t s, bool timed) {
     ctx->bk_hot = nullptr;  // (set by this sort's first level, if it runs one)
     ctx->sub_arith_n[0] = ctx->sub_arith_n[1] = 0;
+    ctx->bk_arith_on = 0;
     ctx->stats = fresh_stats();
     ctx->stats.keys_in = ctx->stats.keys_out = n;
     ctx->stats.tile_sort_keys = n;
@@ -2608,8 +2627,9 @@ static int bucket_sort(dsort_ctx *ctx, const T *d_in, T *d_keys, size_t n, hipSt
     T *direct = sub_keys<T>(ctx) && (const void *)d_in != (const void *)d_keys && n < (1ull << 31) ? d_keys : nullptr;
     uint64_t *hb;
     C *hspl;
+    // (int32: the sorted samples are still in L.smp, so the sort may take the arithmetic map)
     rc = first_level<T>(ctx, d_in, n, 0, part_out, direct, L, sub_keys<T>(ctx) ? 0u : (uint32_t)TILE, s, timed, hb,
-                        hspl);
+                        hspl, false, std::is_same<T, int32_t>::value);
     if (rc) return rc;
     if (const uint64_t m = sub_keys<T>(ctx)) {
         // A bucket between two splitters of the same key holds only that key: it is sorted as it
@@ -3206,6 +3226,20 @@ extern "C" int dsort_debug_sub_arith(const dsort_ctx *ctx, uint32_t out[2]) {
     if (!ctx || !out) return DSORT_EINVAL;
     out[0] = ctx->sub_arith_n[0];
     out[1] = ctx->sub_arith_n[1];
+    return DSORT_OK;
+}
+
+// Likewise the first level's arithmetic bucket map (dsort_bucket.h, BkMap.ar).  mode: -1 by the rule of
+// bucket_slotmap_kernel (default), 0 off, 2 (tests) whenever the samples' key range allows it.
+// out[0] = 1 if the first level of the context's last bucketed sort ran on the map.
+extern "C" int dsort_debug_bucket_arith_mode(dsort_ctx *ctx, int mode) {
+    if (!ctx || (mode != -1 && mode != 0 && mode != 2)) return DSORT_EINVAL;
+    ctx->opt.bk_arith = mode;
+    return DSORT_OK;
+}
+extern "C" int dsort_debug_bucket_arith(const dsort_ctx *ctx, uint32_t out[1]) {
+    if (!ctx || !out) return DSORT_EINVAL;
+    out[0] = ctx->bk_arith_on;
     return DSORT_OK;
 }
 

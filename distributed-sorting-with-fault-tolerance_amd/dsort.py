@@ -554,6 +554,21 @@ class Context:
         self.check(f(self.h, ctypes.cast(out, P)))
         return int(out[0]), int(out[1])
 
+    # Likewise the first level's arithmetic bucket map (csrc/dsort_bucket.h, BkMap.ar).
+    def bucket_arith_mode(self, mode):
+        """-1 = by the sample rule (default), 0 = off, 2 = whenever the samples' key range allows it (tests)."""
+        f = self.lib.dsort_debug_bucket_arith_mode
+        f.restype, f.argtypes = ctypes.c_int, [P, ctypes.c_int]
+        self.check(f(self.h, int(mode)))
+
+    def bucket_arith(self):
+        """True if the first level of the last bucketed sort ran on the arithmetic bucket map."""
+        out = (ctypes.c_uint32 * 1)()
+        f = self.lib.dsort_debug_bucket_arith
+        f.restype, f.argtypes = ctypes.c_int, [P, P]
+        self.check(f(self.h, ctypes.cast(out, P)))
+        return bool(out[0])
+
     @contextlib.contextmanager
     def options(self, **kw):
         """Sets options for the body of a with-statement and restores the previous values."""
